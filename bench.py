@@ -3,7 +3,7 @@
 input (BASELINE.json metric; default workload = configs[2]: "Mask R-CNN R-50-FPN, 1 MI355X, 4-level RoIAlign + 14x14 mask
 head").
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg5|cfg2]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg5|cfg2] [--dump-outputs DIR]
 
 With N > 1 and no launcher environment the script re-executes itself under `python -m torch.distributed.run` with N ranks
 (one per GPU, RCCL); launched by the driver's own torchrun line it just uses the environment it is given.  `n_gpus` in the
@@ -67,7 +67,13 @@ def parse():
     ap.add_argument("--inflight", type=int, default=2, help="steps in flight: consecutive steps (independent batches) are issued round-robin on this many HIP streams, so the latency-bound kernels of one step overlap the RoIAlign launches of another")
     ap.add_argument("--side-steps", type=int, default=100, help="timed steps of each short leg of the OTHER BASELINE configurations (cfg5 channels_last, cfg5 NCHW, cfg2) reported under `other_workloads` of a default cfg3 line at one GPU; 0 = none")
     ap.add_argument("--split", type=int, default=1, help="sub-batches run on separate HIP streams inside one hipGraph (cfg3/cfg5)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "<= 64 MB in all: detections, RoIs, a fixed seeded sample of the pooled-feature rows, mask crops (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def self_launch(a):
@@ -448,6 +454,80 @@ def harder_set_launch(path, feats, top_n, dev, iters):
     return e0.elapsed_time(e1) / iters
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: data bytes written in all (the limit is 64 MB; .npy headers and rounding fit in the rest)
+
+
+def _path_outputs(p, budget, seed):
+    """Host copies (float32 / float64) of what a caller of the region path `p` receives after its last step.  Rows past a count are
+    zeroed (the kernels never write them: what they hold is left over from the allocator).  The pooled features are too large to
+    store whole, so a fixed sample of their rows is taken (indices drawn from RandomState(seed) over every row, stored beside them);
+    the binarised mask crops give their per-detection pixel count, the byte layout and a fixed sample of byte positions."""
+    f32, f64 = (lambda t: t.float().cpu().numpy()), (lambda t: t.cpu().numpy().astype(np.float64))
+    rs = np.random.RandomState(seed)
+    B, T = p.B, p.top_n
+    out = {}
+    n_rois = p.n_rois.cpu().numpy().astype(np.int64)
+    roi_ok = np.arange(T)[None, :] < n_rois[:, None]                                   # [B, T]
+    out["n_rois"] = n_rois.astype(np.float64)
+    out["rois"] = np.where(roi_ok[:, :, None], f32(p.rois5), 0).astype(np.float32)
+    out["roi_levels"] = np.where(roi_ok, f32(p.roi_levels), 0).astype(np.float32)
+    cnt = p.det_count.cpu().numpy().astype(np.int64)
+    D = p.dets.shape[1]
+    det_ok = np.arange(D)[None, :] < np.minimum(cnt, D)[:, None]                      # [B, D]
+    out["det_count"] = cnt.astype(np.float64)
+    out["dets"] = np.where(det_ok[:, :, None], f32(p.dets), 0).astype(np.float32)
+    masks = hasattr(p, "mask_feats")
+    if masks:
+        nbytes = p.mask_bytes.cpu().numpy().astype(np.int64)
+        rects, offs = p.mask_rects.cpu().numpy().astype(np.int64), p.mask_offsets.cpu().numpy().astype(np.int64)
+        area = np.zeros((B, D), np.float64)
+        k_crop = 1 << 16
+        u = rs.uniform(0.0, 1.0, k_crop)
+        crop_sample = np.zeros((B, k_crop), np.float32)
+        for b in range(B):
+            crops = p.crops[b, :int(nbytes[b])].cpu().numpy()
+            for d in np.flatnonzero(det_ok[b]):
+                x0, y0, x1, y1 = rects[b, d]
+                area[b, d] = float(crops[offs[b, d]:offs[b, d] + (x1 - x0) * (y1 - y0)].sum(dtype=np.int64))
+            if crops.size:
+                crop_sample[b] = crops[(u * crops.size).astype(np.int64)]
+        out["mask_bytes"] = nbytes.astype(np.float64)
+        out["mask_boxes"] = np.where(det_ok[:, :, None], f32(p.mask_boxes), 0).astype(np.float32)
+        out["mask_rects"] = np.where(det_ok[:, :, None], rects, 0).astype(np.float32)
+        out["mask_offsets"] = np.where(det_ok, offs, 0).astype(np.float64)
+        out["mask_area"] = area
+        out["mask_crop_sample"] = crop_sample           # byte (u * mask_bytes[b]) of image b's crops, u fixed
+        out["mask_crop_sample_u"] = u
+    left = budget - sum(v.nbytes for v in out.values())
+    feats = [("box_feats", p.box_feats, roi_ok)] + ([("mask_feats", p.mask_feats, det_ok)] if masks else [])
+    for name, t, ok in feats:
+        row_bytes = 4 * int(np.prod(t.shape[1:])) + 8
+        k = max(1, min(t.shape[0], left // len(feats) // row_bytes))
+        idx = np.sort(rs.choice(t.shape[0], k, replace=False))
+        rows = t.index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+        rows[~ok.reshape(-1)[idx]] = 0
+        out[name + "_sample"], out[name + "_sample_index"] = rows, idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(path, out_dir, seed=0):
+    """--dump-outputs DIR: the outputs of `path`'s last step as DIR/<name>.npy (an OverlappedRegionPath: one set per sub-batch,
+    names prefixed split<i>_).  Same arguments -> same inputs, so two builds can be compared file by file."""
+    subs = getattr(path, "sub", None)
+    if subs is None:
+        arrs = _path_outputs(path, DUMP_BYTES, seed)
+    else:
+        arrs = {}
+        for i, sp in enumerate(subs):
+            arrs.update({"split%d_%s" % (i, k): v for k, v in _path_outputs(sp, DUMP_BYTES // len(subs), seed + i).items()})
+    total = sum(v.nbytes for v in arrs.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrs.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -557,6 +637,8 @@ def main():
             raise SystemExit("all-gathered detections differ from the local result")
         if rank == 0:                        # kept for the cross-rank check below (the staging buffers are reused by later steps)
             gathered_copy = (gd.clone(), gc.clone())
+    if a.dump_outputs and rank == 0:         # before anything below runs the paths again
+        dump_outputs(paths[s_last], a.dump_outputs)
     # a longer run of the same loop (>= --sustain-seconds): the contract region is only K steps long
     n_sus = int(max(a.steps, np.ceil(a.sustain_seconds / max(dt / a.steps, 1e-6)))) if a.sustain_seconds > 0 else 0
     if dist is not None and n_sus:

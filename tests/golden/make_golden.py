@@ -76,6 +76,24 @@ def postprocess_logits(ns):
          prob_torch=prob.numpy(), scores_final=scores_final, boxes_final=boxes_final, cls_id=cls_id)
 
 
+def box_voting_many_voters(ns):
+    """boxes.box_voting (boxes.py:280) with hundreds of voters per top det (numpy's pairwise float32 sum beyond 128 elements is on
+    the path): the cases of tests/test_oracle_ref.py::test_bbox_overlaps_and_box_voting_vs_reference, same generator, same draws."""
+    rs = synth.rng(13, 0)
+    for t in range(6):                     # the draws of the test's bbox_overlaps half, so that the voting cases below match it
+        synth.make_rois(rs, 150 + 37 * t); synth.make_rois(rs, 90 + 11 * t)
+    base = np.array([[50, 60, 200, 220], [300, 100, 420, 300], [10, 10, 600, 400]], np.float32)
+    arrs = {}
+    for t in range(4):
+        n = 400 + 300 * t
+        a = base[rs.randint(0, 3, n)] + rs.standard_normal((n, 4)).astype(np.float32) * 3
+        all_d = np.ascontiguousarray(np.hstack([a, rs.uniform(0, 1, (n, 1))]), np.float32)
+        top = np.ascontiguousarray(all_d[rs.choice(n, 10, replace=False)])
+        arrs["all_dets%d" % t], arrs["top_dets%d" % t] = all_d, top
+        arrs["vote%d" % t] = ns.boxes.box_voting(top, all_d, 0.5)
+    save("box_voting_many_voters", **arrs)
+
+
 def main():
     ns = rh.load_reference()
     torch.manual_seed(0)
@@ -83,6 +101,8 @@ def main():
         return bbox_vote(ns)
     if len(sys.argv) > 1 and sys.argv[1] == "postprocess_logits":
         return postprocess_logits(ns)
+    if len(sys.argv) > 1 and sys.argv[1] == "box_voting_many_voters":
+        return box_voting_many_voters(ns)
 
     # ---- A2 anchors (generate_anchors.py:54) -------------------------------------------------------------------
     arrs = {}
@@ -221,6 +241,7 @@ def main():
     save("mask_geometry", **arrs)
     bbox_vote(ns)
     postprocess_logits(ns)
+    box_voting_many_voters(ns)
 
 
 if __name__ == "__main__":

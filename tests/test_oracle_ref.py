@@ -66,10 +66,12 @@ def test_soft_nms_vs_reference_cython(oracle, ref, method):
 
 
 def test_bbox_overlaps_and_box_voting_vs_reference(oracle, ref):
-    """orc_bbox_overlaps vs the reference's own Cython build; orc_box_voting vs lib/utils/boxes.py:280 imported in place
-    (hundreds of voters per top det: numpy's pairwise float32 sum beyond 128 elements is on the path)."""
+    """orc_bbox_overlaps vs the reference's own Cython build; orc_box_voting vs what lib/utils/boxes.py:280 returned on the same
+    inputs (tests/golden/box_voting_many_voters.npz, tests/golden/make_golden.py; hundreds of voters per top det: numpy's pairwise
+    float32 sum beyond 128 elements is on the path)."""
+    from conftest import golden
     _, cb = ref.load_ref_cython()
-    ns = ref.load_reference()
+    g = golden("box_voting_many_voters")
     rs = synth.rng(13, 0)
     for t in range(6):
         b = synth.make_rois(rs, 150 + 37 * t); q = synth.make_rois(rs, 90 + 11 * t)
@@ -80,4 +82,5 @@ def test_bbox_overlaps_and_box_voting_vs_reference(oracle, ref):
         a = base[rs.randint(0, 3, n)] + rs.standard_normal((n, 4)).astype(np.float32) * 3
         all_d = np.ascontiguousarray(np.hstack([a, rs.uniform(0, 1, (n, 1))]), np.float32)
         top = np.ascontiguousarray(all_d[rs.choice(n, 10, replace=False)])
-        assert np.array_equal(oracle.box_voting(top, all_d, 0.5), ns.boxes.box_voting(top, all_d, 0.5))
+        assert np.array_equal(all_d, g["all_dets%d" % t]) and np.array_equal(top, g["top_dets%d" % t]), t
+        assert np.array_equal(oracle.box_voting(top, all_d, 0.5), g["vote%d" % t]), t
