@@ -49,6 +49,7 @@ struct RpnParams {
   RpnLevelDev lv[kRpnMaxLevels];
   int n_levels, batch, chunks_per_image, ties_per_image, k_stride;
   float im_h, im_w, min_size;
+  const float* im_hw;   // [B][2] per-image (h_b, w_b) on the device, or null: every image is (im_h, im_w) -- see SegExtent
   uint32_t* hist;       // [S][2][kHistBins]
   uint32_t* counters;   // [S][2] : selected count, candidate count
   uint64_t* gt_keys;    // [S][k_stride]
@@ -70,6 +71,34 @@ __device__ __forceinline__ int find_level(const RpnParams& p, int chunk) {
   for (int i = 1; i < kRpnMaxLevels; i++)
     if (i < p.n_levels && chunk >= p.lv[i].chunk_begin) l = i;
   return l;
+}
+
+// Per-image size (dtc_rpn_topk_decode_sized): image b of a padded batch behaves as a batch-1 run on its own (h_b, w_b) blob.
+// Only the cells y < ceil(h_b / stride), x < ceil(w_b / stride) of the level map exist, K shrinks to min(K, A * Hb * Wb), and the
+// clip / centre filter use (h_b, w_b).  Sizes are clamped to (im_h, im_w) and the cell extent to the map; h_b or w_b <= 0 leaves
+// no cell (count 0).  Cropping keeps the row-major order of the cells, so the canonical padded-map index (h*W + w)*A + a orders
+// the surviving anchors exactly as the cropped map's own index would: ties break the same way.  Read from device memory by every
+// kernel of the call (a captured graph picks up sizes written in place).  crop == false: the whole map, today's arithmetic.
+struct SegExtent { float h, w; int Hb, Wb, N, K; bool crop; };
+
+__device__ __forceinline__ SegExtent seg_extent(const RpnParams& p, int b, const RpnLevelDev& L) {
+  SegExtent e; e.h = p.im_h; e.w = p.im_w; e.Hb = L.H; e.Wb = L.W; e.N = L.N; e.K = L.K; e.crop = false;
+  if (p.im_hw) {
+    e.h = fminf(p.im_hw[2 * b], p.im_h); e.w = fminf(p.im_hw[2 * b + 1], p.im_w);
+    e.Hb = e.h > 0.f ? min(L.H, (int)ceilf(e.h / L.feat_stride)) : 0;
+    e.Wb = e.w > 0.f ? min(L.W, (int)ceilf(e.w / L.feat_stride)) : 0;
+    if (e.Hb <= 0 || e.Wb <= 0) e.Hb = e.Wb = 0;
+    e.crop = e.Hb < L.H || e.Wb < L.W;
+    e.N = L.A * e.Hb * e.Wb;
+    e.K = min(L.K, e.N);        // L.K = min(pre_nms_top_n, N) (N when <= 0): min(pre_nms_top_n, A*Hb*Wb)
+  }
+  return e;
+}
+// memory index i = (a*H + h)*W + w of a [A,H,W] map inside the extent?
+__device__ __forceinline__ bool in_extent(const SegExtent& e, const RpnLevelDev& L, int i) {
+  if (!e.crop) return true;
+  const int hw = i % (L.H * L.W), h = hw / L.W;
+  return h < e.Hb && hw - h * L.W < e.Wb;
 }
 
 // threshold state after `passes` completed passes: prefix (ordered-key bits found so far) and remaining rank
@@ -136,7 +165,8 @@ __global__ __launch_bounds__(kHistThreads) void rpn_hist_kernel(RpnParams p) {
   const int b = blockIdx.y;
   const int l = find_level(p, blockIdx.x);
   const RpnLevelDev& L = p.lv[l];
-  if (L.K >= L.N) return;  // take everything: no selection needed
+  const SegExtent ext = seg_extent(p, b, L);
+  if (ext.K >= ext.N) return;  // take everything: no selection needed
   const int seg = b * p.n_levels + l;
   const int chunk = blockIdx.x - L.chunk_begin;
   [[maybe_unused]] const int ptb = blockIdx.y * gridDim.x + blockIdx.x;
@@ -153,13 +183,13 @@ __global__ __launch_bounds__(kHistThreads) void rpn_hist_kernel(RpnParams p) {
     v[u] = i < end ? sc[i] : 0.f;
   }
   for (int i = threadIdx.x; i < kHistBins; i += kHistThreads) h[i] = 0;
-  const SelState st = load_state<PASS>(p, seg, (uint32_t)L.K, sh);  // ends with a barrier (or needs one for PASS 0)
+  const SelState st = load_state<PASS>(p, seg, (uint32_t)ext.K, sh);  // ends with a barrier (or needs one for PASS 0)
   if (PASS == 0) __syncthreads();
   DTC_PT(PASS, ptb, 1);
 #pragma unroll
   for (int u = 0; u < kChunk / kHistThreads; u++) {
     const int i = begin + u * kHistThreads + (int)threadIdx.x;
-    if (i < end) {
+    if (i < end && in_extent(ext, L, i)) {
       const uint32_t o = float_to_ordered(v[u]);
       if (PASS == 0) atomicAdd(&h[o >> 20], 1u);
       if (PASS == 1) { if ((o >> 20) == st.p0) atomicAdd(&h[(o >> 8) & 4095u], 1u); }
@@ -188,7 +218,8 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
   const RpnLevelDev& L = p.lv[l];
   const int seg = b * p.n_levels + l;
   const int chunk = blockIdx.x - L.chunk_begin;
-  const bool take_all = L.K >= L.N;
+  const SegExtent ext = seg_extent(p, b, L);
+  const bool take_all = ext.K >= ext.N;
   [[maybe_unused]] const int ptb = blockIdx.y * gridDim.x + blockIdx.x;
   DTC_PT(2, ptb, 0);
   const float* sc = L.cls + (size_t)b * L.N;      // the chunk's scores: requested first, consumed behind the threshold look-up
@@ -202,7 +233,7 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
   if (threadIdx.x < 2) lcnt[threadIdx.x] = 0;
   KeyBand kb; kb.lo = kb.hi = 0;
   if (!take_all) {
-    const SelState st = load_state<2>(p, seg, (uint32_t)L.K, sh);
+    const SelState st = load_state<2>(p, seg, (uint32_t)ext.K, sh);
     const uint32_t bl = ((st.p0 << 12) | st.p1) << 8;
     kb = candidate_band(bl, bl | 0xffu, L.logit != 0, sh);
   }
@@ -212,7 +243,7 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
 #pragma unroll
   for (int u = 0; u < kChunk / kHistThreads; u++) {
     const int i = begin + u * kHistThreads + (int)threadIdx.x;
-    if (i >= end) continue;
+    if (i >= end || !in_extent(ext, L, i)) continue;
     const float s = v[u];
     const uint32_t o = float_to_ordered(s);
     const bool is_gt = take_all || o > kb.hi;
@@ -295,7 +326,7 @@ __global__ __launch_bounds__(kSortDecodeThreads) void rpn_sort_kernel(RpnParams 
   const uint32_t n_cand = p.counters[(size_t)seg * 2 + 1];
   const uint64_t* gt = p.gt_keys + (size_t)seg * p.k_stride;
   const uint64_t* cand = p.cand_keys + (size_t)b * p.ties_per_image + L.tie_begin;
-  const int K = L.K;
+  const int K = seg_extent(p, b, L).K;
   const uint32_t need = (uint32_t)K - n_gt;  // candidates to take (0 when everything is taken)
   // More candidates than the sort holds (a constant map, a saturated sigmoid): the `need` smallest candidate keys are found
   // with a radix select over (a) the 32 score bits, (b) the canonical index among the candidates that share the threshold
@@ -383,6 +414,7 @@ __global__ __launch_bounds__(kDecodeThreads) void rpn_decode_kernel(RpnParams p)
   const int seg = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int b = seg / p.n_levels, l = seg - b * p.n_levels;
   const RpnLevelDev& L = p.lv[l];
+  const SegExtent ext = seg_extent(p, b, L);
   // Block number: a block waits for the blocks BEFORE it, so those must be running.  When the whole grid is co-resident (p.resident:
   // the launcher checks grid <= 1024 workgroups of 256 threads on 256 CUs) the launch index serves and a dependent global round trip
   // goes away; otherwise a run-time TICKET, so that a block only ever waits for blocks that were dispatched before it, whatever order
@@ -422,11 +454,11 @@ __global__ __launch_bounds__(kDecodeThreads) void rpn_decode_kernel(RpnParams p)
     const float ax2 = L.anchors[a * 4 + 2] + sx, ay2 = L.anchors[a * 4 + 3] + sy;
     const float* d = dl + (size_t)(a * 4) * HW + hw;
     decode_box(ax1, ay1, ax2, ay2, d[0], d[HW], d[2 * HW], d[3 * HW], box);
-    box[0] = clip1(box[0], p.im_w - 1.f); box[1] = clip1(box[1], p.im_h - 1.f);   // :230-236
-    box[2] = clip1(box[2], p.im_w - 1.f); box[3] = clip1(box[3], p.im_h - 1.f);
+    box[0] = clip1(box[0], ext.w - 1.f); box[1] = clip1(box[1], ext.h - 1.f);   // :230-236
+    box[2] = clip1(box[2], ext.w - 1.f); box[3] = clip1(box[3], ext.h - 1.f);
     const float ws = box[2] - box[0] + 1.f, hs = box[3] - box[1] + 1.f;           // :155-156
     const float xc = box[0] + fdiv(ws, 2.f), yc = box[1] + fdiv(hs, 2.f);         // :157-158
-    ok = (ws >= p.min_size) && (hs >= p.min_size) && (xc < p.im_w) && (yc < p.im_h);  // :159-162
+    ok = (ws >= p.min_size) && (hs >= p.min_size) && (xc < ext.w) && (yc < ext.h);  // :159-162
   }
   const uint64_t m = __ballot(ok);
   if (lane == 0) wave_tot[wv] = __builtin_popcountll(m);
@@ -535,6 +567,14 @@ DTC_API size_t dtc_rpn_topk_decode_workspace_bytes(const dtc_rpn_level* levels, 
 DTC_API int dtc_rpn_topk_decode(const dtc_rpn_level* levels, int n_levels, int batch, float im_h, float im_w,
                                 float min_size_scaled, void* workspace, size_t workspace_bytes, float* out_boxes,
                                 float* out_scores, int32_t* out_counts, int k_stride, dtc_stream_t stream) {
+  return dtc_rpn_topk_decode_sized(levels, n_levels, batch, im_h, im_w, nullptr, min_size_scaled, workspace, workspace_bytes,
+                                   out_boxes, out_scores, out_counts, k_stride, stream);
+}
+
+DTC_API int dtc_rpn_topk_decode_sized(const dtc_rpn_level* levels, int n_levels, int batch, float im_h, float im_w,
+                                      const float* im_hw, float min_size_scaled, void* workspace, size_t workspace_bytes,
+                                      float* out_boxes, float* out_scores, int32_t* out_counts, int k_stride,
+                                      dtc_stream_t stream) {
   if (!levels || !workspace || !out_boxes || !out_scores || !out_counts) return DTC_EINVAL;
   dtc::RpnParams p;
   dtc::RpnPlan plan;
@@ -545,7 +585,7 @@ DTC_API int dtc_rpn_topk_decode(const dtc_rpn_level* levels, int n_levels, int b
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
   p.n_levels = n_levels; p.batch = batch; p.chunks_per_image = plan.chunks_per_image;
   p.ties_per_image = plan.ties_per_image; p.k_stride = plan.k_stride;
-  p.im_h = im_h; p.im_w = im_w; p.min_size = min_size_scaled;
+  p.im_h = im_h; p.im_w = im_w; p.im_hw = im_hw; p.min_size = min_size_scaled;
   p.hist = reinterpret_cast<uint32_t*>(w + plan.off_hist);
   p.counters = reinterpret_cast<uint32_t*>(w + plan.off_counters);
   p.gt_keys = reinterpret_cast<uint64_t*>(w + plan.off_gt);

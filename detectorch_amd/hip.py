@@ -85,6 +85,8 @@ def lib():
     L.dtc_rpn_topk_decode_workspace_bytes.restype = sz
     L.dtc_rpn_topk_decode.argtypes = [C.POINTER(RpnLevel), i, i, f, f, f, p, sz, p, p, p, i, p]
     L.dtc_rpn_topk_decode.restype = i
+    L.dtc_rpn_topk_decode_sized.argtypes = [C.POINTER(RpnLevel), i, i, f, f, p, f, p, sz, p, p, p, i, p]
+    L.dtc_rpn_topk_decode_sized.restype = i
     L.dtc_gather_kept.argtypes = [p, p, i, i, p, p, i, p, p, p]
     L.dtc_gather_kept.restype = i
     ll = C.c_longlong
@@ -329,13 +331,15 @@ def make_rpn_levels(cls_probs, bbox_preds, anchors, feat_strides, pre_nms_top_n,
 
 
 def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w, pre_nms_top_n, post_nms_top_n,
-                       nms_thresh, min_size_scaled=0.0, scores_are_logits=False):
+                       nms_thresh, min_size_scaled=0.0, scores_are_logits=False, im_hw=None):
     """Batched multi-level GenerateProposals (generate_proposals.py:31-122) with zero host round trips.
     scores_are_logits=True folds the RPN head's sigmoid (detector.py:125) into the top-k: pass the raw logits, get the
     proposals and PROBABILITY scores the reference would produce from sigmoid(logits), without materialising them.
 
     Returns (boxes [B,L,P,4], scores [B,L,P], counts int32 [B,L]) with P = post_nms_top_n (rows >= count undefined),
     plus the pre-NMS (sorted) boxes/scores/counts for callers that want them.
+    im_hw [B,2] (h_b, w_b) per image (dtc_rpn_topk_decode_sized): image b of the padded batch gives what a batch-1 call on its
+    own (h_b, w_b) blob gives; None: every image is (im_h, im_w).
     """
     dev = _require_cuda(*cls_probs, *bbox_preds)
     L_ = lib()
@@ -352,11 +356,13 @@ def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w,
     pre_boxes = torch.empty((S, kmax, 4), dtype=torch.float32, device=dev)
     pre_scores = torch.empty((S, kmax), dtype=torch.float32, device=dev)
     pre_counts = torch.empty((S,), dtype=torch.int32, device=dev)
+    if im_hw is not None:
+        im_hw = torch.as_tensor(im_hw, dtype=torch.float32).to(dev).reshape(B, 2).contiguous()
     with torch.cuda.device(dev):
-        rc = L_.dtc_rpn_topk_decode(lv, nl, B, float(im_h), float(im_w), float(min_size_scaled), ws.data_ptr(),
-                                    ws.numel(), pre_boxes.data_ptr(), pre_scores.data_ptr(), pre_counts.data_ptr(),
-                                    kmax, stream_ptr(dev))
-    check(rc, "dtc_rpn_topk_decode")
+        rc = L_.dtc_rpn_topk_decode_sized(lv, nl, B, float(im_h), float(im_w), _ptr(im_hw), float(min_size_scaled),
+                                          ws.data_ptr(), ws.numel(), pre_boxes.data_ptr(), pre_scores.data_ptr(),
+                                          pre_counts.data_ptr(), kmax, stream_ptr(dev))
+    check(rc, "dtc_rpn_topk_decode_sized")
     if nms_thresh <= 0:                                   # generate_proposals.py:114
         return (pre_boxes.view(B, nl, kmax, 4), pre_scores.view(B, nl, kmax), pre_counts.view(B, nl),
                 pre_boxes, pre_scores, pre_counts)

@@ -514,11 +514,14 @@ class detector(nn.Module):
         return self._paths[key]
 
     @torch.no_grad()
-    def forward_batched(self, images, scaling_factor, im_size):
+    def forward_batched(self, images, scaling_factor, im_size, blob_hw=None):
         """Mask / Faster R-CNN FPN forward for a BATCH (lib/model/detector.py:233-286 + :99-112 + eval_mask_FPN.ipynb:231-262,
         which the reference runs image by image with 21 synchronising copies each).
           images [B,3,H,W] prepared blobs of one padded size (utils.blob.im_list_to_blob); scaling_factor [B]; im_size [B,2]
-          = original (h, w) per image.
+          = original (h, w) per image.  blob_hw [B,2]: each image's own blob size (h_b, w_b) inside the padded one -- for FPN its
+          resized size rounded up to the stride 32 (hip.prep_images' sizes); the RPN of image b then clips, filters and ranks
+          exactly as a batch-1 run on that blob would (dtc_rpn_topk_decode_sized; RoIAlign still reads the padded maps).  None:
+          every image is the whole blob.
         Everything stays on the device:  backbone(B) -> RPN heads -> FpnRegionPath.launch_proposals (top-k, NMS, collect,
         distribute, RoIAlign 7x7 in visiting order) -> fc6/fc7/cls/bbox -> launch_detections (softmax folded in, class decode,
         80-class NMS, top-100, mask-branch RoIAlign 14x14) -> mask head convs -> launch_masks (paste, binarise, COCO RLE).
@@ -544,7 +547,7 @@ class detector(nn.Module):
             img_features = feats
         path = self._region_path(B, h, w, dev)
         path.bind_rpn([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox], feats,
-                      scores_are_logits=self.fuse_rpn_sigmoid)
+                      scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
         path.launch_proposals()
         x = self._head(path.box_feats)                                              # [B*1000, 1024]
         T = path.top_n

@@ -21,6 +21,13 @@ from . import hip, synth
 from .utils.generate_anchors import generate_anchors
 
 
+def _device_hw(im_hw, B, dev):
+    """Per-image (h, w) sizes -> an owned float32 [B,2] device tensor (None stays None: the dtc_rpn_topk_decode_sized NULL path)."""
+    if im_hw is None:
+        return None
+    return torch.as_tensor(im_hw, dtype=torch.float32).to(dev).reshape(B, 2).clone().contiguous()
+
+
 class FpnRegionPath:
     def __init__(self, batch, device, channels=256, n_cls=81, pre_nms_top_n=1000, post_nms_top_n=1000,
                  collect_top_n=1000, rpn_nms_thresh=0.7, max_det=100, max_out=128, mask_res=28,
@@ -98,8 +105,12 @@ class FpnRegionPath:
     # The three stages can also be bound / launched one by one by a model that runs its head GEMMs / convs in between
     # (detectorch_amd.model.detector.forward_batched):  launch_proposals -> box head -> launch_detections -> mask head ->
     # launch_masks.
-    def bind_rpn(self, rpn_cls, rpn_bbox, feats, scores_are_logits=False):
+    def bind_rpn(self, rpn_cls, rpn_bbox, feats, scores_are_logits=False, im_hw=None):
+        """im_hw [B,2]: each image's own blob size (h_b, w_b) inside the padded batch (dtc_rpn_topk_decode_sized); its
+        proposals are those of a batch-1 run on that blob.  Kept in the device tensor self.rpn_im_hw, which every launch (and a
+        captured graph) reads: sizes written into it in place apply to the next step.  None: every image is (pad_h, pad_w)."""
         self.rpn_cls, self.rpn_bbox, self.feats = rpn_cls, rpn_bbox, feats
+        self.rpn_im_hw = _device_hw(im_hw, self.B, self.dev)
         self.rpn_lv, self._alive = hip.make_rpn_levels(rpn_cls, rpn_bbox, self.anchors, self.strides, [self.pre] * 5,
                                                        scores_are_logits=scores_are_logits)
         need = hip.lib().dtc_rpn_topk_decode_workspace_bytes(self.rpn_lv, 5, self.B, self.kmax)
@@ -125,9 +136,9 @@ class FpnRegionPath:
         L, B, ck = hip.lib(), self.B, hip.check
         st = st or hip.stream_ptr(self.dev)
         S, T = B * 5, self.top_n
-        ck(L.dtc_rpn_topk_decode(self.rpn_lv, 5, B, float(self.pad_h), float(self.pad_w), 0.0, self.rpn_ws.data_ptr(),
-                                 self.rpn_ws.numel(), self.pre_boxes.data_ptr(), self.pre_scores.data_ptr(),
-                                 self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
+        ck(L.dtc_rpn_topk_decode_sized(self.rpn_lv, 5, B, float(self.pad_h), float(self.pad_w), hip._ptr(self.rpn_im_hw), 0.0,
+                                       self.rpn_ws.data_ptr(), self.rpn_ws.numel(), self.pre_boxes.data_ptr(),
+                                       self.pre_scores.data_ptr(), self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
         ck(L.dtc_nms_sorted(self.pre_boxes.data_ptr(), self.pre_counts.data_ptr(), S, self.kmax, self.rpn_thresh, self.P,
                             self.nms_ws.data_ptr(), self.nms_ws.numel(), self.keep.data_ptr(), self.P,
                             self.keep_cnt.data_ptr(), st), "nms_sorted")
@@ -324,8 +335,10 @@ class C4RegionPath:
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
         self.det_ws = hip.workspace(L.dtc_postprocess_detections_workspace_bytes(B, T, n_cls), dev)
 
-    def bind(self, rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, scaling_factor, im_size):
+    def bind(self, rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, scaling_factor, im_size, im_hw=None):
+        """im_hw [B,2]: each image's own size inside the padded batch, kept in self.rpn_im_hw (see FpnRegionPath.bind_rpn)."""
         self.rpn_cls, self.rpn_bbox, self.feat = rpn_cls, rpn_bbox, feat
+        self.rpn_im_hw = _device_hw(im_hw, self.B, self.dev)
         self.cls_score, self.bbox_pred, self.sf, self.im_size = cls_score, bbox_pred, scaling_factor, im_size
         self.rpn_lv, self._alive = hip.make_rpn_levels([rpn_cls], [rpn_bbox], self.anchors, [16.0], [self.pre])
         self.rpn_ws = hip.workspace(hip.lib().dtc_rpn_topk_decode_workspace_bytes(self.rpn_lv, 1, self.B, self.kmax), self.dev)
@@ -336,9 +349,9 @@ class C4RegionPath:
     def _launch(self):
         L, B, st, ck = hip.lib(), self.B, hip.stream_ptr(self.dev), hip.check
         T, D = self.top_n, self.max_out
-        ck(L.dtc_rpn_topk_decode(self.rpn_lv, 1, B, float(self.im_h), float(self.im_w), 0.0, self.rpn_ws.data_ptr(),
-                                 self.rpn_ws.numel(), self.pre_boxes.data_ptr(), self.pre_scores.data_ptr(),
-                                 self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
+        ck(L.dtc_rpn_topk_decode_sized(self.rpn_lv, 1, B, float(self.im_h), float(self.im_w), hip._ptr(self.rpn_im_hw), 0.0,
+                                       self.rpn_ws.data_ptr(), self.rpn_ws.numel(), self.pre_boxes.data_ptr(),
+                                       self.pre_scores.data_ptr(), self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
         ck(L.dtc_nms_sorted(self.pre_boxes.data_ptr(), self.pre_counts.data_ptr(), B, self.kmax, self.thresh, self.P,
                             self.nms_ws.data_ptr(), self.nms_ws.numel(), self.keep.data_ptr(), self.P,
                             self.keep_cnt.data_ptr(), st), "nms_sorted")

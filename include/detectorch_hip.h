@@ -169,6 +169,16 @@ size_t dtc_rpn_topk_decode_workspace_bytes(const dtc_rpn_level* levels, int n_le
 int dtc_rpn_topk_decode(const dtc_rpn_level* levels, int n_levels, int batch, float im_h, float im_w,
                         float min_size_scaled, void* workspace, size_t workspace_bytes, float* out_boxes,
                         float* out_scores, int32_t* out_counts, int k_stride, dtc_stream_t stream);
+/* dtc_rpn_topk_decode with a size per image: im_hw is a DEVICE float32 [batch, 2] array of (h_b, w_b), read by the kernels at run
+ * time (a captured hipGraph picks up sizes written in place), or NULL: every image is (im_h, im_w), exactly dtc_rpn_topk_decode.
+ * Image b of a padded batch then gives what a batch-1 call on its own (h_b, w_b) blob would: at each level only the anchor cells
+ * y < ceil(h_b / feat_stride), x < ceil(w_b / feat_stride) take part, the per-segment top-n is min(pre_nms_top_n, A * H_b * W_b),
+ * boxes are clipped to (w_b - 1, h_b - 1) and centre-filtered against (w_b, h_b).  Ties keep the ascending (h,w,a) order (row-major
+ * order survives the crop).  Sizes above (im_h, im_w) are clamped to it and the cell extent to the map; h_b <= 0 or w_b <= 0 gives
+ * count 0.  The level maps, k_stride and the workspace are those of the padded batch. */
+int dtc_rpn_topk_decode_sized(const dtc_rpn_level* levels, int n_levels, int batch, float im_h, float im_w, const float* im_hw,
+                              float min_size_scaled, void* workspace, size_t workspace_bytes, float* out_boxes,
+                              float* out_scores, int32_t* out_counts, int k_stride, dtc_stream_t stream);
 
 /* proposals[keep] / scores[keep] of generate_proposals.py:119-120 for every segment: out_boxes [n_seg, keep_stride, 4],
  * out_scores [n_seg, keep_stride] (rows >= keep_count[s] untouched). */

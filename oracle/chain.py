@@ -3,6 +3,7 @@
 TEST INFRASTRUCTURE ONLY: the checker for detectorch_amd.pipeline.FpnRegionPath (tests/, smoke()) and the thing timed by
 bench.py's cpu_baseline leg.  Follows lib/model/detector.py:240-270 + eval_mask_FPN.ipynb:231-262 of the reference.
 """
+import math
 import time
 
 import numpy as np
@@ -13,10 +14,23 @@ FPN_STRIDES = (4.0, 8.0, 16.0, 32.0, 64.0)
 ROI_SCALES = (0.25, 0.125, 0.0625, 0.03125)
 
 
+def crop_rpn_map(m, prop_hw, stride):
+    """The part of a [A',H,W] RPN map that an image of blob size prop_hw = (h, w) has on its own: the cells
+    y < ceil(h / stride), x < ceil(w / stride) (contiguous copy)."""
+    h, w = prop_hw
+    return np.ascontiguousarray(m[:, :math.ceil(h / stride), :math.ceil(w / stride)])
+
+
 def fpn_hot_path(rpn_cls, rpn_bbox, feats, cls_score, bbox_pred, masks, sf, im_size, pad_h, pad_w, pre=1000, post=1000,
-                 top_n=1000, max_det=100, M=28, box_p=7, mask_p=14, sr=2, timings=None, roi_align=None):
+                 top_n=1000, max_det=100, M=28, box_p=7, mask_p=14, sr=2, timings=None, roi_align=None, prop_hw=None):
     """rpn_cls/rpn_bbox: 5 arrays [A,H,W]/[4A,H,W]; feats: 4 arrays [1,C,H,W]; cls_score [top_n,81]; bbox_pred [top_n,324];
-    masks [>=D,81,M,M].  Returns a dict of every intermediate the GPU path produces."""
+    masks [>=D,81,M,M].  Returns a dict of every intermediate the GPU path produces.
+    prop_hw = (h, w): the image's own blob size inside a padded batch -- the proposals are those of a batch-1 run on that blob
+    (RPN maps cropped to it, clip and filter against it), while RoIAlign keeps reading the padded maps in `feats`."""
+    if prop_hw is not None:
+        rpn_cls = [crop_rpn_map(m, prop_hw, FPN_STRIDES[l]) for l, m in enumerate(rpn_cls)]
+        rpn_bbox = [crop_rpn_map(m, prop_hw, FPN_STRIDES[l]) for l, m in enumerate(rpn_bbox)]
+        pad_h, pad_w = prop_hw
     t = time.perf_counter
     T = {} if timings is None else timings
     ra = roi_align or orc.roi_align_forward       # bench.py passes the reference-compiled loop (oracle/_ref) when it is there
@@ -107,9 +121,13 @@ def compare_with_gpu(path, b, ref, im_h, im_w, check_masks=True):
 
 
 def c4_hot_path(rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, sf, im_size, im_h, im_w, pre=6000, post=1000, pooled=7, sr=0,
-                max_det=100, timings=None, roi_align=None):
+                max_det=100, timings=None, roi_align=None, prop_hw=None):
     """BASELINE configs[1] (Faster R-CNN R-50-C4) for ONE image: rpn_cls [15,H,W], rpn_bbox [60,H,W], feat [1,C,H,W].
-    Follows lib/model/detector.py:240-248, 273-284 (C4 branch) + lib/utils/result_utils.py:76-168."""
+    Follows lib/model/detector.py:240-248, 273-284 (C4 branch) + lib/utils/result_utils.py:76-168.
+    prop_hw = (h, w): the image's own size inside a padded batch (see fpn_hot_path); RoIAlign reads the padded `feat`."""
+    if prop_hw is not None:
+        rpn_cls, rpn_bbox = crop_rpn_map(rpn_cls, prop_hw, 16.0), crop_rpn_map(rpn_bbox, prop_hw, 16.0)
+        im_h, im_w = prop_hw
     t = time.perf_counter
     T = {} if timings is None else timings
     ra = roi_align or orc.roi_align_forward

@@ -247,3 +247,40 @@ def test_forward_batched_bf16_backbone_feeds_roialign_and_heads_without_a_cast()
                                                      out32.data_ptr(), hip.DTC_F32, hip.stream_ptr()), "packed bf16 -> fp32")
     torch.cuda.synchronize()
     assert torch.equal(out32.to(torch.bfloat16), p.box_feats)
+
+
+def test_forward_batched_mixed_sizes_clips_each_image_to_its_own_blob():
+    """Two images of different shapes prepared into one padded blob by hip.prep_images; blob_hw = each image's own stride-32
+    blob.  Every RoI of image b lies inside that blob, and image b's proposals (pre- and post-NMS, every level) equal
+    hip.generate_proposals on the RPN maps the path was bound to, cropped to image b with the scalars (h_b, w_b).  (Not compared
+    with a batch-1 forward: conv numerics at the padding differ, see test_forward_batched_batch2_and_bf16_head.)"""
+    import math
+    from detectorch_amd import hip
+    model = _boost(_fpn_model())
+    g = torch.Generator(device="cuda"); g.manual_seed(8)
+    raw = [torch.randint(0, 256, (240, 400, 3), generator=g, device="cuda", dtype=torch.uint8),
+           torch.randint(0, 256, (400, 240, 3), generator=g, device="cuda", dtype=torch.uint8)]
+    blob, scales, resized = hip.prep_images(raw, target_size=320, max_size=448)
+    blob_hw = [(32 * math.ceil(h / 32), 32 * math.ceil(w / 32)) for (h, w) in resized]
+    assert blob_hw[0] != blob_hw[1] and tuple(blob.shape[2:]) == (448, 448)
+    sf = torch.tensor(scales, device="cuda")
+    im_size = torch.tensor([[240.0, 400.0], [400.0, 240.0]], device="cuda")
+    path = model.forward_batched(blob, sf, im_size, blob_hw=blob_hw)
+    torch.cuda.synchronize()
+    logits = model.fuse_rpn_sigmoid
+    for b, (h, w) in enumerate(blob_hw):
+        n = int(path.n_rois[b])
+        rois = path.rois5[b, :n, 1:]
+        assert n > 0 and float(rois.min()) >= 0
+        assert float(rois[:, 2].max()) <= w - 1 and float(rois[:, 3].max()) <= h - 1
+        crop = lambda m, s: m[b:b + 1, :, :math.ceil(h / s), :math.ceil(w / s)].contiguous()
+        ref = hip.generate_proposals([crop(c, s) for c, s in zip(path.rpn_cls, path.strides)],
+                                     [crop(d, s) for d, s in zip(path.rpn_bbox, path.strides)], path.anchors, path.strides,
+                                     h, w, [path.pre] * 5, path.post, path.rpn_thresh, scores_are_logits=logits)
+        rb, rs, rc, rpb, rps, rpc = ref
+        for l in range(5):
+            s = b * 5 + l
+            k, m = int(path.pre_counts[s]), int(path.keep_cnt[s])
+            assert k == int(rpc[l]) and m == int(rc[0, l]), (b, l)
+            assert torch.equal(path.pre_scores[s, :k], rps[l, :k]) and torch.equal(path.pre_boxes[s, :k], rpb[l, :k])
+            assert torch.equal(path.prop_scores[s, :m], rs[0, l, :m]) and torch.equal(path.prop_boxes[s, :m], rb[0, l, :m])

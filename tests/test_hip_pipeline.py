@@ -317,3 +317,79 @@ def test_more_ties_than_rows_raise_or_truncate(oracle):
         boxes, _ = result_utils.assemble_results(path.dets, path.det_count, on_overflow="truncate")
     # (the rows past the true count are zero rows of class 0 here: the count was faked)
     assert sum(len(boxes[j][1]) for j in range(1, 81)) == int((path.dets[1, :, 5] >= 1).sum())
+
+
+# ---- mixed-size batches: image b's proposals are those of a batch-1 run on its own blob (h_b, w_b); RoIAlign keeps reading the
+# padded batch maps (Detectron-style batched inference), so box features are pinned against the oracle RoIAlign on image b's
+# slice of the padded map, not on a crop
+MIXED_HW = [(800, 1344), (512, 1344), (800, 576), (96, 160)]
+
+
+def _pad_scores_above(maps, sizes, strides, g):
+    """maps: per level [B,A,H,W] probabilities: halve them, then give the cells outside image b's extent values in [0.75, 0.95)
+    (above every cell inside), so that proposals ranked / clipped against the padded blob differ from the batch-1 ones."""
+    for m, s in zip(maps, strides):
+        m.mul_(0.5)
+        for b, (h, w) in enumerate(sizes):
+            out = torch.ones(m.shape[2:], dtype=torch.bool, device=m.device)
+            out[:-(-h // s), :-(-w // s)] = False
+            hi = 0.75 + 0.2 * torch.rand(m[b].shape, generator=g, device=m.device)
+            m[b].copy_(torch.where(out, hi, m[b]))
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_fpn_region_path_mixed_sizes_vs_oracle_chain(oracle, use_graph):
+    import chain
+    from detectorch_amd import synth
+    from detectorch_amd.pipeline import FpnRegionPath, synthetic_batch
+    dev = torch.device("cuda", 0)
+    B, C = len(MIXED_HW), 8
+    path = FpnRegionPath(B, dev, channels=C)
+    inputs = list(synthetic_batch(B, dev, seed=3400, channels=C))
+    g = torch.Generator(device=dev); g.manual_seed(3401)
+    _pad_scores_above(inputs[0], MIXED_HW, synth.FPN_STRIDES, g)
+    inputs[7] = torch.tensor([[h / 1.6, w / 1.6] for (h, w) in MIXED_HW], device=dev)      # original sizes (sf = 1.6)
+    path.bind_rpn(inputs[0], inputs[1], inputs[2], im_hw=MIXED_HW)
+    path.bind_heads(*inputs[3:5], inputs[6], inputs[7])
+    path.bind_masks(inputs[5])
+    rpn_cls, rpn_bbox, feats, cls_score, bbox_pred, masks, sf, im_size = [
+        [t.cpu().numpy() for t in x] if isinstance(x, list) else x.cpu().numpy() for x in inputs]
+    rounds = [MIXED_HW] + ([[MIXED_HW[3], MIXED_HW[0], (320, 480), MIXED_HW[1]]] if use_graph else [])
+    for r, sizes in enumerate(rounds):
+        if r:      # new sizes written IN PLACE into the tensor the captured graph reads
+            path.rpn_im_hw.copy_(torch.tensor(sizes, dtype=torch.float32))
+        path.step(use_graph=use_graph)
+        torch.cuda.synchronize()
+        for b in range(B):
+            ref = chain.fpn_hot_path([c[b] for c in rpn_cls], [d[b] for d in rpn_bbox], [f[b:b + 1] for f in feats],
+                                     cls_score[b], bbox_pred[b], masks[b * path.max_out:(b + 1) * path.max_out], sf[b],
+                                     im_size[b], path.pad_h, path.pad_w, prop_hw=sizes[b])
+            assert ref["rois"].shape[0] > 0
+            assert chain.compare_with_gpu(path, b, ref, int(im_size[b, 0]), int(im_size[b, 1]))
+            n = int(path.n_rois[b])
+            rois = path.rois5[b, :n, 1:].cpu().numpy()
+            assert rois[:, 2].max() <= sizes[b][1] - 1 and rois[:, 3].max() <= sizes[b][0] - 1
+
+
+def test_c4_region_path_mixed_sizes_vs_oracle_chain(oracle):
+    import chain
+    from detectorch_amd.pipeline import C4RegionPath, synthetic_c4_batch
+    dev = torch.device("cuda", 0)
+    sizes = [(800, 1333), (480, 640)]
+    B, C = len(sizes), 16
+    path = C4RegionPath(B, dev, channels=C)
+    inputs = list(synthetic_c4_batch(B, dev, seed=2700, channels=C))
+    g = torch.Generator(device=dev); g.manual_seed(2701)
+    _pad_scores_above([inputs[0]], sizes, [16], g)
+    path.bind(*inputs, im_hw=sizes)
+    path.step(use_graph=True)
+    path.step(use_graph=True)
+    torch.cuda.synchronize()
+    rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, sf, im_size = [x.cpu().numpy() for x in inputs]
+    for b in range(B):
+        ref = chain.c4_hot_path(rpn_cls[b], rpn_bbox[b], feat[b:b + 1], cls_score[b], bbox_pred[b], sf[b], im_size[b],
+                                path.im_h, path.im_w, prop_hw=sizes[b])
+        assert chain.compare_c4_with_gpu(path, b, ref)
+        assert ref["rois"].shape[0] > 500
+        n = int(path.n_rois[b])
+        assert path.rois5[b, :n, 3].max() <= sizes[b][1] - 1 and path.rois5[b, :n, 4].max() <= sizes[b][0] - 1
