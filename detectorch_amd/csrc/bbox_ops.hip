@@ -7,22 +7,12 @@
 // where the reference stores into a DTYPE_t variable; iw*ih is a float32 product; the division is IEEE float32.
 // box_voting reproduces numpy's evaluation order: the weighted coordinate sums add the voters in index order (axis-0
 // reduction of the [m,4] product), the weight sum is numpy's pairwise float32 summation.
+#include "box_vote.h"
 #include "dtc_common.h"
 
 namespace dtc {
 
-__device__ __forceinline__ double span1(float hi, float lo) { return (double)(hi - lo) + 1.0; }
-
-// one element of bbox_overlaps: box B vs query Q (cython_bbox.pyx:54-74)
-__device__ __forceinline__ float iou_bbox(float4 B, float4 Q) {
-  const float box_area = (float)(span1(Q.z, Q.x) * span1(Q.w, Q.y));          // :54-57
-  const float iw = (float)span1(fminf(B.z, Q.z), fmaxf(B.x, Q.x));            // :59-62
-  if (!(iw > 0.f)) return 0.f;
-  const float ih = (float)span1(fminf(B.w, Q.w), fmaxf(B.y, Q.y));            // :64-67
-  if (!(ih > 0.f)) return 0.f;
-  const float ua = (float)(span1(B.z, B.x) * span1(B.w, B.y) + (double)box_area - (double)(iw * ih));   // :69-73
-  return fdiv(iw * ih, ua);                                                   // :74
-}
+// span1 / iou_bbox / np_sum_f32 / box_vote_one: box_vote.h
 
 __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restrict__ boxes, int n, int box_stride,
                                                             const float* __restrict__ query, int k, int query_stride,
@@ -50,41 +40,6 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restr
 
 constexpr int kVoteMax = 8192;     // all_dets per call (LDS voter list: 32 KB)
 
-// numpy float32 pairwise add-reduce over ws[vl[i]] (see oracle/oracle.c:np_pairwise_sum_f32), explicit stack instead of
-// recursion: blocks of <= 128 elements, split at n/2 rounded down to a multiple of 8.
-__device__ float np_sum_f32(const float* all, const int* vl, int n) {
-  auto W = [&](int i) { return all[(size_t)vl[i] * 5 + 4]; };
-  auto leaf = [&](int s, int m) {
-    if (m < 8) {
-      float r = 0.f;
-      for (int i = 0; i < m; i++) r += W(s + i);
-      return r;
-    }
-    float r0 = W(s), r1 = W(s + 1), r2 = W(s + 2), r3 = W(s + 3), r4 = W(s + 4), r5 = W(s + 5), r6 = W(s + 6), r7 = W(s + 7);
-    int i = 8;
-    for (; i < m - (m % 8); i += 8) {
-      r0 += W(s + i); r1 += W(s + i + 1); r2 += W(s + i + 2); r3 += W(s + i + 3);
-      r4 += W(s + i + 4); r5 += W(s + i + 5); r6 += W(s + i + 6); r7 += W(s + i + 7);
-    }
-    float res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < m; i++) res += W(s + i);
-    return res;
-  };
-  int fs[16], fn[16], fstage[16];
-  float val[16];
-  int sp = 0, vp = 0;
-  fs[0] = 0; fn[0] = n; fstage[0] = 0; sp = 1;
-  while (sp > 0) {
-    const int s = fs[sp - 1], m = fn[sp - 1];
-    if (m <= 128) { val[vp++] = leaf(s, m); sp--; continue; }
-    int n2 = m / 2; n2 -= n2 % 8;
-    if (fstage[sp - 1] == 0) { fstage[sp - 1] = 1; fs[sp] = s; fn[sp] = n2; fstage[sp] = 0; sp++; }
-    else if (fstage[sp - 1] == 1) { fstage[sp - 1] = 2; fs[sp] = s + n2; fn[sp] = m - n2; fstage[sp] = 0; sp++; }
-    else { const float b = val[--vp]; const float a = val[--vp]; val[vp++] = a + b; sp--; }
-  }
-  return val[0];
-}
-
 // one wave per top det
 __global__ __launch_bounds__(64) void box_voting_kernel(const float* __restrict__ top, int t, const float* __restrict__ all,
                                                         int a, float thresh, float* __restrict__ out,
@@ -94,32 +49,11 @@ __global__ __launch_bounds__(64) void box_voting_kernel(const float* __restrict_
   const float* tp = top + (size_t)k * 5;
   const float4 B = make_float4(tp[0], tp[1], tp[2], tp[3]);
   int m = 0;
-  for (int j0 = 0; j0 < a; j0 += 64) {
-    const int j = j0 + lane;
-    bool vote = false;
-    if (j < a) {
-      const float* ap = all + (size_t)j * 5;
-      vote = iou_bbox(B, make_float4(ap[0], ap[1], ap[2], ap[3])) >= thresh;          // boxes.py:292
-    }
-    const uint64_t bal = __ballot(vote);
-    if (vote) vl[m + __builtin_popcountll(bal & ((1ull << lane) - 1ull))] = j;
-    m += __builtin_popcountll(bal);
-  }
-  __syncthreads();
-  float res = 0.f;
-  if (lane < 4) {            // weighted coordinate sums: voters in index order (axis-0 reduce of boxes * ws[:, None])
-    float acc = 0.f;
-    for (int i = 0; i < m; i++) {
-      const float* ap = all + (size_t)vl[i] * 5;
-      const float prod = ap[lane] * ap[4];
-      acc = i == 0 ? prod : acc + prod;
-    }
-    res = acc;
-  }
-  float scl = 0.f;
-  if (lane == 4 && m > 0) scl = np_sum_f32(all, vl, m);                                // ws.sum(): numpy pairwise
-  scl = __shfl(scl, 4, 64);
-  if (lane < 4) out[(size_t)k * 5 + lane] = m > 0 ? fdiv(res, scl) : tp[lane];        // :295 np.average
+  const float v = box_vote_one(
+      B, lane < 4 ? tp[lane] : 0.f, a, thresh, [](int) { return true; },
+      [&](int j) { const float* ap = all + (size_t)j * 5; return make_float4(ap[0], ap[1], ap[2], ap[3]); },
+      [&](int j, int c) { return all[(size_t)j * 5 + c]; }, [&](int j) { return all[(size_t)j * 5 + 4]; }, vl, lane, &m);
+  if (lane < 4) out[(size_t)k * 5 + lane] = v;                                         // :295 np.average
   if (lane == 4) out[(size_t)k * 5 + 4] = tp[4];                                       // 'ID' scoring: score unchanged
   if (lane == 5 && n_voters) n_voters[k] = m;
 }

@@ -9,10 +9,27 @@
 //                    four waves, greedy walk by one, later columns marked by all (round 4; until then a separate launch pair)
 //   det_finalize     grid (image): max_detections_per_img limit (:154-163) = radix select of the 100-th largest score,
 //                    `>=` filter (ties kept, like the reference), class-major / roi-ascending output (:165).
+//
+// Test-time options (dtc_postprocess_detections_ex, dtc_det_options; the reference's do_soft_nms / do_bbox_vote, :133-153):
+//   Soft-NMS         det_candidates stops after the compaction and the decode and writes the candidates in dets_j order (roi
+//                    ascending, :127-132) from the candidate bitmap; det_soft_nms (one wave per (class, image) segment) runs the
+//                    single-segment walk of soft_nms_walk.h on an LDS copy (25 B per candidate: <= 100 KB at R = 4096) and
+//                    publishes the kept rows in SELECTION order as the same (ordered decayed score, roi) keys the hard NMS
+//                    writes; det_finalize's limit is unchanged and its output keeps the per-class selection order (:143, :165).
+//                    One wave per segment and not the four-wave workgroup of the hard NMS: the walk is one dependent pick after
+//                    another with a barrier each, which extra waves cannot shorten.
+//   bbox voting      ('ID' scoring) never changes a score, and the per-image limit depends on the scores alone, so the rows that
+//                    survive the limit are the same whether the vote comes before or after it: det_vote votes only the <= max_out
+//                    EMITTED rows (one wave per row, box_vote.h -- the single-segment drop-in's body) against every candidate of
+//                    the row's segment (the undecayed dets_j, :150), rewrites the box and det_rois_scaled; with the FPN mask
+//                    mapping requested the mapping runs after the vote, on the voted boxes (det_fpn_map, one more launch).
+//   Launch count is fixed per option set (graph capture): + det_soft_nms with Soft-NMS, + det_vote (+ det_fpn_map) with voting.
 #include "block_sort.h"
+#include "box_vote.h"
 #include "dtc_common.h"
 #include "fpn_map.h"
 #include "radix_select.h"
+#include "soft_nms_walk.h"
 
 namespace dtc {
 DTC_PT_TABLE(detections)
@@ -43,7 +60,13 @@ struct DetParams {
   int32_t* keep_count;       // [S]
   float nms_thresh;
   int np2_max;               // next_pow2(R): the sort keys occupy the first np2_max * 8 bytes of the dynamic LDS
+  // options (dtc_det_options): soft -> no sort / NMS here, q_roi[seg, k] = roi of the k-th candidate in dets_j order (det_soft_nms
+  // reads it); cand_bits (soft or voting, else NULL) -> the candidate bitmap of the segment, bit r of word r / 64
+  int soft;
+  uint64_t* cand_bits;       // [S, 64]
 };
+
+constexpr int kCandWords = 64;   // bitmap words per segment: R <= 4096
 
 // lib/utils/boxes.py:168-208 for one (roi, class)
 __device__ __forceinline__ void decode_det(const float roi[4], float sf, const float* d, float wx, float wy, float ww,
@@ -90,6 +113,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
   __shared__ int running;
+  __shared__ uint64_t cbits_s[kCandWords];
   const int j = blockIdx.x + 1, b = blockIdx.y;
   const int seg = b * (p.n_cls - 1) + (j - 1);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -127,6 +151,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       const float s = sv[u];
       const bool ok = r < nr && s > p.score_thresh;
       const uint64_t m = __ballot(ok);
+      if (p.cand_bits && lane == 0) cbits_s[((R0 + u * kDetThreads) >> 6) + wv] = m;     // rois [64 w, 64 w + 64): w < 64
       if (m == 0ull) continue;                                 // uniform per wave
       int base = 0;
       if (lane == 0) base = atomicAdd(&running, __builtin_popcountll(m));
@@ -145,22 +170,14 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     if (n == 0) p.keep_count[seg] = 0;
   }
   DTC_PT(0, ptb, 1);
+  const int nw = (nr + 63) >> 6;
+  if (p.cand_bits)
+    for (int w = tid; w < nw; w += kDetThreads) p.cand_bits[(size_t)seg * kCandWords + w] = cbits_s[w];
   if (n == 0) return;
-  const int np2 = next_pow2(n);
-  for (int i = n + tid; i < np2; i += kDetThreads) keys[i] = kPadKey;
-  block_bitonic_sort<kDetThreads>(keys, np2);
-  DTC_PT(0, ptb, 2);
-  // the box of rank k (decoded once): to q_boxes[r] for det_finalize, and in SCORE order for the NMS below -- in LDS when the segment
-  // has at most kNmsLdsCap candidates (the usual tens to a few hundred), else in the global scratch p.sorted_boxes (LDS sized for
-  // every possible segment would leave 2 workgroups per CU)
   float4* qb = reinterpret_cast<float4*>(p.q_boxes) + (size_t)seg * p.R;
-  float4* sbox_l = reinterpret_cast<float4*>(smem + (size_t)p.np2_max * sizeof(uint64_t));     // [kNmsLdsCap]
-  float4* sorted_g = reinterpret_cast<float4*>(p.sorted_boxes) + (size_t)seg * p.R;
-  const bool in_lds = n <= kNmsLdsCap;
   const float sf = p.decoded ? 1.f : p.scale[b];
   const float im_h = p.decoded ? 0.f : p.im_size[b * 2 + 0], im_w = p.decoded ? 0.f : p.im_size[b * 2 + 1];
-  for (int k = tid; k < n; k += kDetThreads) {
-    const int r = (int)desc_key_index(keys[k]);
+  auto box_of = [&](int r) {
     float4 v;
     if (p.decoded) {        // lib/utils/result_utils.py:128: boxes[inds, j * 4:(j + 1) * 4] taken as they are
       const float* d = p.decoded + ((size_t)b * p.R + r) * 4 * p.n_cls + 4 * j;
@@ -173,6 +190,42 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       decode_det(rr, sf, d, p.wx, p.wy, p.ww, p.wh, im_h, im_w, o);
       v = make_float4(o[0], o[1], o[2], o[3]);
     }
+    return v;
+  };
+  if (p.soft) {
+    // Soft-NMS input: the candidates in dets_j order (np.where is ascending, :127) -- an ordered compaction of the bitmap: wave 0
+    // scans the popcounts of the <= 64 words, each lane lists its word's rois; then every thread decodes
+    uint32_t* lst = reinterpret_cast<uint32_t*>(smem);        // over the (unused) sort keys: n * 4 <= np2_max * 8 bytes
+    if (wv == 0) {
+      uint64_t w = lane < nw ? cbits_s[lane] : 0ull;
+      const int pc = __builtin_popcountll(w);
+      int incl = pc;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+      int k = incl - pc;
+      while (w) { lst[k++] = (uint32_t)(lane * 64 + __builtin_ctzll(w)); w &= w - 1ull; }
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += kDetThreads) {
+      const int r = (int)lst[k];
+      qb[r] = box_of(r);
+      p.q_roi[(size_t)seg * p.R + k] = r;
+    }
+    return;
+  }
+  const int np2 = next_pow2(n);
+  for (int i = n + tid; i < np2; i += kDetThreads) keys[i] = kPadKey;
+  block_bitonic_sort<kDetThreads>(keys, np2);
+  DTC_PT(0, ptb, 2);
+  // the box of rank k (decoded once): to q_boxes[r] for det_finalize, and in SCORE order for the NMS below -- in LDS when the segment
+  // has at most kNmsLdsCap candidates (the usual tens to a few hundred), else in the global scratch p.sorted_boxes (LDS sized for
+  // every possible segment would leave 2 workgroups per CU)
+  float4* sbox_l = reinterpret_cast<float4*>(smem + (size_t)p.np2_max * sizeof(uint64_t));     // [kNmsLdsCap]
+  float4* sorted_g = reinterpret_cast<float4*>(p.sorted_boxes) + (size_t)seg * p.R;
+  const bool in_lds = n <= kNmsLdsCap;
+  for (int k = tid; k < n; k += kDetThreads) {
+    const int r = (int)desc_key_index(keys[k]);
+    const float4 v = box_of(r);
     qb[r] = v;                                               // by roi index (global, det_finalize)
     if (in_lds) sbox_l[k] = v; else sorted_g[k] = v;         // score order (the NMS)
   }
@@ -283,6 +336,31 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
   }
 }
 
+// ---- Soft-NMS of the (class, image) segments (cython_nms.soft_nms via box_utils.soft_nms, result_utils.py:133-140): one wavefront per
+// segment walks the single-segment drop-in's algorithm (soft_nms_walk.h) on an LDS copy of the segment's dets_j, then publishes the
+// survivors in selection order as (ordered decayed score, roi) keys: det_finalize reads them exactly like the hard NMS's kept keys
+__global__ __launch_bounds__(64) void det_soft_nms_kernel(DetParams p, float sigma, float Nt, float threshold, int method) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int seg = blockIdx.y * (p.n_cls - 1) + blockIdx.x, lane = threadIdx.x;
+  const int n = p.cand_count[seg];
+  if (n == 0) { if (lane == 0) p.keep_count[seg] = 0; return; }
+  const SoftNmsLds a = soft_nms_lds_arrays(smem, n);
+  const float4* qb = reinterpret_cast<const float4*>(p.q_boxes) + (size_t)seg * p.R;
+  const float* qs = p.q_scores + (size_t)seg * p.R;
+  const int32_t* ql = p.q_roi + (size_t)seg * p.R;
+  for (int k = lane; k < n; k += 64) {
+    const int r = ql[k];
+    const float4 v = qb[r];
+    a.X1[k] = v.x; a.Y1[k] = v.y; a.X2[k] = v.z; a.Y2[k] = v.w; a.S[k] = qs[r]; a.I[k] = r; a.dead[k] = 0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  __syncthreads();
+  const int N = soft_nms_walk(a.X1, a.Y1, a.X2, a.Y2, a.S, a.I, a.dead, n, sigma, Nt, threshold, method, lane);
+  uint64_t* K = p.kept_key + (size_t)seg * p.R;
+  for (int k = lane; k < N; k += 64) K[k] = make_desc_key(a.S[k], (uint32_t)a.I[k]);
+  if (lane == 0) p.keep_count[seg] = N;
+}
+
 constexpr int kFinThreads = 1024;
 constexpr int kFinMaxCls = 256;
 
@@ -299,6 +377,7 @@ struct FinParams {
   float* det_rois_scaled;     // [B, max_out, 4]  boxes * scaling_factor (eval_mask_FPN.ipynb:249), may be NULL
   int32_t* det_count;         // [B]
   FpnMapOut fm;               // fm.on: also emit the FPN level mapping of the detection rows (the mask branch's rois), fpn_map.h
+  int soft;                   // kept_key in selection order with DECAYED scores (det_soft_nms): rows of a class in that order
 };
 
 // off[c] = sum of cnt(c') for c' < c, c = 0 .. nseg (off[nseg] = total); one wavefront, nseg <= 256.
@@ -381,13 +460,13 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
       const int n_c = cnt_r[k], base = koff[c];
       if (lane < n_c) {
         const uint32_t o = ~(uint32_t)(key_r[k] >> 32);
-        st_key[base + lane] = o; st_cq[base + lane] = ((uint32_t)c << 12) | desc_key_index(key_r[k]);
+        st_key[base + lane] = o; st_cq[base + lane] = ((uint32_t)c << 12) | (p.soft ? (uint32_t)lane : desc_key_index(key_r[k]));
         atomicAdd(&h0[o >> 21], 1u);                          // the first pass of the limit's radix select, while the entry is in hand
       }
       for (int e = 64 + lane; e < n_c; e += 64) {             // a crowded class: the rest of its entries, one more round trip
         uint32_t o; int q;
         fetch(c, e, o, q);
-        st_key[base + e] = o; st_cq[base + e] = ((uint32_t)c << 12) | (uint32_t)q;
+        st_key[base + e] = o; st_cq[base + e] = ((uint32_t)c << 12) | (uint32_t)(p.soft ? e : q);
         atomicAdd(&h0[o >> 21], 1u);
       }
     }
@@ -421,13 +500,23 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
   DTC_PT(1, b, 2);
   const float sf = p.scale ? p.scale[b] : 1.f;
   float4* sbox_fm = reinterpret_cast<float4*>(&bitmap[0][0]);     // fast path + fm.on: the scaled boxes by output row (max_out <= 512)
-  auto emit = [&](int slot, int c, int q, bool to_lds) {      // one detection row (:143 dets_j[keep], :165 vstack)
+  // one detection row (:143 dets_j[keep], :165 vstack).  Soft segments: `e` is the position in the class's kept list (selection
+  // order), the roi and the decayed score come from its key; otherwise q is the roi and the score the candidate's own
+  auto emit = [&](int slot, int c, int q, bool to_lds, int e = -1) {
     const int seg = seg0 + c;
+    float score;
+    if (e >= 0) {
+      const uint64_t key = p.kept_key[(size_t)seg * p.R + e];
+      q = (int)desc_key_index(key);
+      score = desc_key_score(key);
+    } else {
+      score = p.q_scores[(size_t)seg * p.R + q];
+    }
     const float4 bx = reinterpret_cast<const float4*>(p.q_boxes)[(size_t)seg * p.R + q];
     if (to_lds) sbox_fm[slot] = make_float4(bx.x * sf, bx.y * sf, bx.z * sf, bx.w * sf);
     float* o = p.dets + ((size_t)b * p.max_out + slot) * 6;
     o[0] = bx.x; o[1] = bx.y; o[2] = bx.z; o[3] = bx.w;
-    o[4] = p.q_scores[(size_t)seg * p.R + q];
+    o[4] = score;
     o[5] = (float)(c + 1);
     p.det_roi[(size_t)b * p.max_out + slot] = q;                               // the candidate index IS the roi index (round 6)
     if (p.det_rois_scaled)
@@ -460,7 +549,10 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
           const uint4 v = reinterpret_cast<const uint4*>(surv)[j];
           rank += (v.x < me ? 1 : 0) + (v.y < me ? 1 : 0) + (v.z < me ? 1 : 0) + (v.w < me ? 1 : 0);
         }
-        if (rank < p.max_out) emit(rank, (int)(me >> 12), (int)(me & 4095u), p.fm.on != 0);
+        if (rank < p.max_out) {
+          if (p.soft) emit(rank, (int)(me >> 12), 0, p.fm.on != 0, (int)(me & 4095u));
+          else emit(rank, (int)(me >> 12), (int)(me & 4095u), p.fm.on != 0);
+        }
       }
     }
   }
@@ -501,6 +593,23 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
   for (int c = wv; c < nseg; c += kFinThreads / 64) {
     const int nk = koff[c + 1] - koff[c];
     if (ccnt[c] == 0) continue;
+    if (p.soft) {            // Soft-NMS: the class's kept list in selection order, filtered by `>= T` (ballot + popcount prefix)
+      int slot0 = coff[c];
+      for (int e0 = 0; e0 < nk; e0 += 64) {
+        const int e = e0 + lane;
+        bool ok = false;
+        if (e < nk) {
+          uint32_t o;
+          if (staged) o = st_key[koff[c] + e]; else { int q; fetch(c, e, o, q); }
+          ok = o >= T;                                                       // :161 `>=`
+        }
+        const uint64_t bal = __ballot(ok);
+        const int slot = slot0 + __builtin_popcountll(bal & ((1ull << lane) - 1ull));
+        if (ok && slot < p.max_out) emit(slot, c, 0, false, e);
+        slot0 += __builtin_popcountll(bal);
+      }
+      continue;
+    }
     uint64_t* bm = bitmap[wv];
     bm[lane] = 0;
     __builtin_amdgcn_wave_barrier();
@@ -542,13 +651,62 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
   DTC_PT(1, b, 5);
 }
 
+// ---- bbox voting of the emitted rows (box_utils.box_voting(nms_dets, dets_j, thresh, 'ID'), result_utils.py:145-151): one wavefront per
+// output row; the voters are the row's segment's candidates in dets_j order (roi ascending: the bitmap), weighted by their undecayed
+// scores.  Rewrites dets[:, :4] and det_rois_scaled (the emit's arithmetic); the score, class and det_roi stay.
+struct VoteParams {
+  const int32_t* n_rois;      // [B] or NULL
+  const uint64_t* cand_bits;  // [S, 64]
+  const float* q_boxes;       // [S, R, 4]
+  const float* q_scores;      // [S, R]
+  const float* scale;         // [B] or NULL (1)
+  const int32_t* det_count;   // [B]
+  float* dets;                // [B, max_out, 6]
+  float* det_rois_scaled;     // [B, max_out, 4] or NULL
+  int R, n_cls, max_out;
+  float thresh;
+};
+
+__global__ __launch_bounds__(64) void det_vote_kernel(VoteParams p) {
+  __shared__ int vl[4096];
+  const int row = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  if (row >= min(p.det_count[b], p.max_out)) return;
+  float* d = p.dets + ((size_t)b * p.max_out + row) * 6;
+  const float4 B = make_float4(d[0], d[1], d[2], d[3]);
+  const int seg = b * (p.n_cls - 1) + ((int)d[5] - 1);
+  const int nr = p.n_rois ? min(p.n_rois[b], p.R) : p.R;
+  const uint64_t* bits = p.cand_bits + (size_t)seg * kCandWords;
+  const float4* qb = reinterpret_cast<const float4*>(p.q_boxes) + (size_t)seg * p.R;
+  const float* qs = p.q_scores + (size_t)seg * p.R;
+  int m = 0;
+  const float v = box_vote_one(
+      B, lane < 4 ? d[lane] : 0.f, nr, p.thresh, [&](int r) { return ((bits[r >> 6] >> (r & 63)) & 1ull) != 0ull; },
+      [&](int r) { return qb[r]; },
+      [&](int r, int c) { return reinterpret_cast<const float*>(p.q_boxes)[((size_t)seg * p.R + r) * 4 + c]; },
+      [&](int r) { return qs[r]; }, vl, lane, &m);
+  if (lane < 4) {
+    d[lane] = v;
+    if (p.det_rois_scaled) p.det_rois_scaled[((size_t)b * p.max_out + row) * 4 + lane] = v * (p.scale ? p.scale[b] : 1.f);
+  }
+}
+
+// the FPN level mapping of the (voted) rows, when the vote took it out of det_finalize: what fm.on does there, from det_rois_scaled
+constexpr int kMapThreads = kFpnMapMaxRows + 64;     // fpn_map_rows: blockDim >= D + 4 pads the scan
+__global__ __launch_bounds__(kMapThreads) void det_fpn_map_kernel(FpnMapOut fm, const float* det_rois_scaled, const int32_t* det_count,
+                                                                  int max_out) {
+  __shared__ __attribute__((aligned(16))) uint32_t code_s[kFpnMapMaxRows + 4], key_s[kFpnMapMaxRows + 4];
+  const int b = blockIdx.x;
+  const float4* ds = reinterpret_cast<const float4*>(det_rois_scaled) + (size_t)b * max_out;
+  fpn_map_rows(fm, b, max_out, min(det_count[b], max_out), [&](int t) { return ds[t]; }, code_s, key_s);
+}
+
 static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace dtc
 
 namespace dtc {
-struct DetPlan { size_t sorted_boxes, q_boxes, q_scores, q_roi, cand_count, kept_key, keep_count, sm_stats, total; };
-static DetPlan det_plan(int batch, int R, int n_cls) {
+struct DetPlan { size_t sorted_boxes, q_boxes, q_scores, q_roi, cand_count, kept_key, keep_count, sm_stats, cand_bits, total; };
+static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits = false) {
   DetPlan d;
   const size_t S = (size_t)batch * (n_cls - 1);
   size_t o = 0;
@@ -560,6 +718,7 @@ static DetPlan det_plan(int batch, int R, int n_cls) {
   d.kept_key = o; o += al256(S * R * sizeof(uint64_t));
   d.keep_count = o; o += al256(S * sizeof(int32_t));
   d.sm_stats = o; o += al256((size_t)batch * R * 2 * sizeof(double));
+  d.cand_bits = o; if (with_bits) o += al256(S * kCandWords * sizeof(uint64_t));
   d.total = o;
   return d;
 }
@@ -570,12 +729,36 @@ DTC_API size_t dtc_postprocess_detections_workspace_bytes(int batch, int max_roi
   return dtc::det_plan(batch, max_rois, n_cls).total;
 }
 
+// dtc_det_options validation (host only) -> DTC_OK / DTC_EINVAL; *soft = Soft-NMS walk method (0 hard, 1 linear, 2 gaussian) or -1
+static int det_options_check(const dtc_det_options* opt, int* soft, bool* vote) {
+  *soft = -1; *vote = false;
+  if (!opt) return DTC_OK;
+  if (opt->nms_method < 0 || opt->nms_method > 3) return DTC_EINVAL;
+  if (opt->nms_method == 2 && !(opt->soft_sigma > 0.f)) return DTC_EINVAL;
+  if (opt->bbox_vote != 0 && opt->bbox_vote != 1) return DTC_EINVAL;
+  if (opt->bbox_vote && !(opt->bbox_vote_thresh > 0.f && opt->bbox_vote_thresh <= 1.f)) return DTC_EINVAL;
+  *soft = opt->nms_method == 0 ? -1 : opt->nms_method == 3 ? 0 : opt->nms_method;
+  *vote = opt->bbox_vote != 0;
+  return DTC_OK;
+}
+
+DTC_API size_t dtc_postprocess_detections_ex_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt) {
+  int soft;
+  bool vote;
+  if (batch < 1 || max_rois < 1 || n_cls < 2 || det_options_check(opt, &soft, &vote) != DTC_OK) return 0;
+  return dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote).total;
+}
+
 static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
                                        const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor, const float* im_size,
                                        int batch, int max_rois, int n_cls, float wx, float wy, float ww, float wh,
                                        float score_thresh, float nms_thresh, int max_det, void* workspace,
                                        size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
-                                       int32_t* det_count, int max_out, dtc_stream_t stream, const dtc_fpn_map_out* fpn = nullptr) {
+                                       int32_t* det_count, int max_out, dtc_stream_t stream, const dtc_fpn_map_out* fpn = nullptr,
+                                       const dtc_det_options* opt = nullptr) {
+  int soft;
+  bool vote;
+  if (det_options_check(opt, &soft, &vote) != DTC_OK) return DTC_EINVAL;
   if (batch < 0 || max_rois < 1 || n_cls < 2 || n_cls - 1 > dtc::kFinMaxCls || max_out < 1) return DTC_EINVAL;
   if (fpn) {
     if (!det_rois_scaled || !fpn->rois5 || !fpn->roi_levels || !fpn->n_out || !fpn->rois_by_level || !fpn->level_counts || !fpn->idx_restore ||
@@ -588,7 +771,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   if (!cls_score || !workspace || !dets || !det_roi || !det_count) return DTC_EINVAL;
   if (!decoded_boxes && (!rois5 || !bbox_pred || !scaling_factor || !im_size)) return DTC_EINVAL;
   if (decoded_boxes && det_rois_scaled) return DTC_EINVAL;
-  const dtc::DetPlan pl = dtc::det_plan(batch, max_rois, n_cls);
+  const dtc::DetPlan pl = dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote);
   if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -617,13 +800,22 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   uint64_t* kept_key = reinterpret_cast<uint64_t*>(w + pl.kept_key);
   int32_t* keep_count = reinterpret_cast<int32_t*>(w + pl.keep_count);
   p.kept_key = kept_key; p.keep_count = keep_count; p.nms_thresh = nms_thresh; p.np2_max = np2;
+  p.soft = soft >= 0 ? 1 : 0;
+  p.cand_bits = soft >= 0 || vote ? reinterpret_cast<uint64_t*>(w + pl.cand_bits) : nullptr;
   hipLaunchKernelGGL(dtc::det_candidates_kernel, dim3(n_cls - 1, batch), dim3(dtc::kDetThreads), smem, s, p);
   DTC_CHECK_LAUNCH();
+  if (soft >= 0) {
+    DTC_RAISE_LDS_ONCE(dtc::det_soft_nms_kernel, 160 * 1024);
+    hipLaunchKernelGGL(dtc::det_soft_nms_kernel, dim3(n_cls - 1, batch), dim3(64), dtc::soft_nms_lds_bytes(max_rois), s, p,
+                       opt->soft_sigma, nms_thresh, opt->soft_score_thresh, soft);
+    DTC_CHECK_LAUNCH();
+  }
   dtc::FinParams f;
   f.kept_key = kept_key; f.keep_count = keep_count; f.q_boxes = p.q_boxes; f.q_scores = p.q_scores;
   f.q_roi = p.q_roi; f.scale = scaling_factor; f.R = max_rois; f.n_cls = n_cls; f.max_det = max_det; f.max_out = max_out;
   f.dets = dets; f.det_roi = det_roi; f.det_rois_scaled = det_rois_scaled; f.det_count = det_count;
-  f.fm.on = fpn ? 1 : 0;
+  f.fm.on = fpn && !vote ? 1 : 0;            // with voting the mapping follows the vote (det_fpn_map)
+  f.soft = soft >= 0 ? 1 : 0;
   if (fpn) {
     f.fm.rois5 = fpn->rois5; f.fm.roi_levels = fpn->roi_levels; f.fm.n_out = fpn->n_out; f.fm.rois_by_level = fpn->rois_by_level;
     f.fm.level_counts = fpn->level_counts; f.fm.idx_restore = fpn->idx_restore; f.fm.roi_order = fpn->roi_order;
@@ -637,6 +829,20 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   if (fsm > 16 * 1024) { DTC_RAISE_LDS_ONCE(dtc::det_finalize_kernel, 116 * 1024); }      // + ~37 KB static: under the 160 KB of a CU
   hipLaunchKernelGGL(dtc::det_finalize_kernel, dim3(batch), dim3(dtc::kFinThreads), fsm, s, f, stage_cap);
   DTC_CHECK_LAUNCH();
+  if (vote) {
+    dtc::VoteParams v;
+    v.n_rois = n_rois; v.cand_bits = p.cand_bits; v.q_boxes = p.q_boxes; v.q_scores = p.q_scores;
+    v.scale = decoded_boxes ? nullptr : scaling_factor; v.det_count = det_count; v.dets = dets; v.det_rois_scaled = det_rois_scaled;
+    v.R = max_rois; v.n_cls = n_cls; v.max_out = max_out; v.thresh = opt->bbox_vote_thresh;
+    hipLaunchKernelGGL(dtc::det_vote_kernel, dim3(max_out, batch), dim3(64), 0, s, v);
+    DTC_CHECK_LAUNCH();
+    if (fpn) {
+      dtc::FpnMapOut fm = f.fm;
+      fm.on = 1;
+      hipLaunchKernelGGL(dtc::det_fpn_map_kernel, dim3(batch), dim3(dtc::kMapThreads), 0, s, fm, det_rois_scaled, det_count, max_out);
+      DTC_CHECK_LAUNCH();
+    }
+  }
   return DTC_OK;
 }
 
@@ -682,4 +888,17 @@ DTC_API int dtc_box_results_nms_limit(const float* scores, const float* boxes, c
   return postprocess_detections_impl(nullptr, n_rois, scores, 0, nullptr, boxes, nullptr, nullptr, batch, max_rois, n_cls, 1.f, 1.f,
                                      1.f, 1.f, score_thresh, nms_thresh, max_det, workspace, workspace_bytes, dets, det_roi,
                                      nullptr, det_count, max_out, stream);
+}
+
+DTC_API int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
+                                          const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor,
+                                          const float* im_size, int batch, int max_rois, int n_cls, float wx, float wy, float ww,
+                                          float wh, float score_thresh, float nms_thresh, int max_det, const dtc_det_options* opt,
+                                          void* workspace, size_t workspace_bytes, float* dets, int32_t* det_roi,
+                                          float* det_rois_scaled, int32_t* det_count, int max_out, const dtc_fpn_map_out* fpn,
+                                          dtc_stream_t stream) {
+  if (decoded_boxes && fpn) return DTC_EINVAL;           // the mapping reads det_rois_scaled, which the decoded-boxes form has not
+  return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, decoded_boxes, scaling_factor,
+                                     im_size, batch, max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace,
+                                     workspace_bytes, dets, det_roi, det_rois_scaled, det_count, max_out, stream, fpn, opt);
 }

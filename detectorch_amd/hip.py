@@ -44,6 +44,27 @@ class FpnMapOut(C.Structure):
                 ("k_min", C.c_int32), ("k_max", C.c_int32)]
 
 
+class DetOptions(C.Structure):
+    """struct dtc_det_options (include/detectorch_hip.h)"""
+    _fields_ = [("nms_method", C.c_int32), ("soft_sigma", C.c_float), ("soft_score_thresh", C.c_float),
+                ("bbox_vote", C.c_int32), ("bbox_vote_thresh", C.c_float)]
+
+
+SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2, "hard": 3}
+
+
+def det_options(do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8):
+    """The reference's test-time options of box_results_with_nms_and_limit (lib/utils/result_utils.py:96-168) as a
+    dtc_det_options, or None for the default (hard NMS, no voting).  The Soft-NMS score floor is the reference's 0.0001 (:138);
+    voting is 'ID' scoring."""
+    if not do_soft_nms and not do_bbox_vote:
+        return None
+    if do_soft_nms and soft_nms_method not in SOFT_NMS_METHODS:
+        raise ValueError("Unknown soft_nms method: %s" % (soft_nms_method,))
+    return DetOptions(SOFT_NMS_METHODS[soft_nms_method] if do_soft_nms else 0, float(soft_nms_sigma), 0.0001,
+                      1 if do_bbox_vote else 0, float(bbox_vote_thresh))
+
+
 _lib = None
 
 
@@ -111,6 +132,11 @@ def lib():
     L.dtc_postprocess_detections_fpn.restype = i
     L.dtc_box_results_nms_limit.argtypes = [p, p, p, i, i, i, f, f, i, p, sz, p, p, p, i, p]
     L.dtc_box_results_nms_limit.restype = i
+    L.dtc_postprocess_detections_ex_workspace_bytes.argtypes = [i, i, i, C.POINTER(DetOptions)]
+    L.dtc_postprocess_detections_ex_workspace_bytes.restype = sz
+    L.dtc_postprocess_detections_ex.argtypes = [p, p, p, i, p, p, p, p, i, i, i, f, f, f, f, f, f, i, C.POINTER(DetOptions), p,
+                                                sz, p, p, p, p, i, C.POINTER(FpnMapOut), p]
+    L.dtc_postprocess_detections_ex.restype = i
     L.dtc_bias_act.argtypes = [p, p, p, i, i, i, i, i, i, i, i, p]
     L.dtc_bias_act.restype = i
     L.dtc_mask_paste.argtypes = [p, p, i, i, p, p, p, i, i, f, i, p, ll, p, p, p, p, p]
@@ -411,18 +437,30 @@ def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max
     return out
 
 
+def det_workspace_bytes(batch, max_rois, n_cls, opt=None):
+    """dtc_postprocess_detections_ex_workspace_bytes (opt: a DetOptions or None)"""
+    need = lib().dtc_postprocess_detections_ex_workspace_bytes(int(batch), int(max_rois), int(n_cls), opt)
+    if need == 0:
+        raise ValueError("invalid detection post-processing shape or options")
+    return need
+
+
 def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size, weights=(10., 10., 5., 5.),
-                           score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None, scores_are_logits=False):
-    """dtc_postprocess_detections.  rois5 [B,R,5], cls_score [B,R,C], bbox_pred [B,R,4C], scaling_factor [B], im_size [B,2].
+                           score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None, scores_are_logits=False,
+                           do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False,
+                           bbox_vote_thresh=0.8):
+    """dtc_postprocess_detections_ex.  rois5 [B,R,5], cls_score [B,R,C], bbox_pred [B,R,4C], scaling_factor [B], im_size [B,2].
     scores_are_logits=True: cls_score holds the raw cls_score-layer output and the softmax of detector.py:281 is folded into
-    the kernel (dtc_postprocess_detections_logits); the probability map is never materialised.
+    the kernel; the probability map is never materialised.  do_soft_nms / soft_nms_sigma / soft_nms_method / do_bbox_vote /
+    bbox_vote_thresh: the reference's options of box_results_with_nms_and_limit (result_utils.py:96-168; 'ID' vote scoring).
     -> (dets [B,max_out,6], det_roi [B,max_out], det_rois_scaled [B,max_out,4], det_count [B])"""
     dev = _require_cuda(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size)
     B, R, ncls = cls_score.shape
     if max_out is None:
         max_out = 128 if max_det > 0 else R * (ncls - 1)
     L_ = lib()
-    need = L_.dtc_postprocess_detections_workspace_bytes(B, R, ncls)
+    opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
+    need = det_workspace_bytes(B, R, ncls, opt)
     if ws is None or ws.numel() < need:
         ws = workspace(need, dev)
     f32, i32 = torch.float32, torch.int32
@@ -433,24 +471,26 @@ def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, 
     rois5, cls_score, bbox_pred = rois5.contiguous(), cls_score.contiguous(), bbox_pred.contiguous()
     scaling_factor, im_size = scaling_factor.to(f32).contiguous(), im_size.to(f32).contiguous()
     with torch.cuda.device(dev):
-        fn = L_.dtc_postprocess_detections_logits if scores_are_logits else L_.dtc_postprocess_detections
-        rc = fn(rois5.data_ptr(), _ptr(n_rois), cls_score.data_ptr(), bbox_pred.data_ptr(),
-                                           scaling_factor.data_ptr(), im_size.data_ptr(), B, R, ncls,
-                                           *[float(w) for w in weights], float(score_thresh), float(nms_thresh),
-                                           int(max_det), ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(),
-                                           det_scaled.data_ptr(), det_count.data_ptr(), int(max_out), stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections")
+        rc = L_.dtc_postprocess_detections_ex(rois5.data_ptr(), _ptr(n_rois), cls_score.data_ptr(), 1 if scores_are_logits else 0,
+                                              bbox_pred.data_ptr(), None, scaling_factor.data_ptr(), im_size.data_ptr(), B, R, ncls,
+                                              *[float(w) for w in weights], float(score_thresh), float(nms_thresh), int(max_det),
+                                              opt, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(),
+                                              det_scaled.data_ptr(), det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
+    check(rc, "dtc_postprocess_detections_ex")
     return dets, det_roi, det_scaled, det_count
 
 
-def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None):
-    """dtc_box_results_nms_limit: scores [B,R,C], decoded boxes [B,R,4C] -> (dets [B,max_out,6], det_roi [B,max_out], det_count [B])"""
+def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None,
+                          do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8):
+    """box_results_with_nms_and_limit on decoded boxes (dtc_postprocess_detections_ex with decoded_boxes): scores [B,R,C],
+    decoded boxes [B,R,4C] -> (dets [B,max_out,6], det_roi [B,max_out], det_count [B]).  Options as postprocess_detections."""
     dev = _require_cuda(scores, boxes, n_rois)
     B, R, ncls = scores.shape
     if max_out is None:
         max_out = 128 if max_det > 0 else R * (ncls - 1)
     L_ = lib()
-    need = L_.dtc_postprocess_detections_workspace_bytes(B, R, ncls)
+    opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
+    need = det_workspace_bytes(B, R, ncls, opt)
     if ws is None or ws.numel() < need:
         ws = workspace(need, dev)
     dets = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
@@ -458,10 +498,11 @@ def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thr
     det_count = torch.empty((B,), dtype=torch.int32, device=dev)
     scores, boxes = scores.contiguous(), boxes.contiguous()
     with torch.cuda.device(dev):
-        rc = L_.dtc_box_results_nms_limit(scores.data_ptr(), boxes.data_ptr(), _ptr(n_rois), B, R, ncls, float(score_thresh),
-                                          float(nms_thresh), int(max_det), ws.data_ptr(), ws.numel(), dets.data_ptr(),
-                                          det_roi.data_ptr(), det_count.data_ptr(), int(max_out), stream_ptr(dev))
-    check(rc, "dtc_box_results_nms_limit")
+        rc = L_.dtc_postprocess_detections_ex(None, _ptr(n_rois), scores.data_ptr(), 0, None, boxes.data_ptr(), None, None, B, R,
+                                              ncls, 1., 1., 1., 1., float(score_thresh), float(nms_thresh), int(max_det), opt,
+                                              ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(), None,
+                                              det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
+    check(rc, "dtc_postprocess_detections_ex")
     return dets, det_roi, det_count
 
 

@@ -496,9 +496,10 @@ class detector(nn.Module):
         return super().load_state_dict(*args, **kw)
 
     # ---- batched entry: B images, zero host round trips ------------------------------------------------------------------
-    def _region_path(self, B, h, w, dev):
+    def _region_path(self, B, h, w, dev, det_options=None):
         from ..pipeline import FpnRegionPath
-        key = (B, h, w, str(dev), self.max_out)
+        # the detection options are baked into the path's launches (and its captured graph): part of the key
+        key = (B, h, w, str(dev), self.max_out, tuple(sorted((det_options or {}).items())))
         if key in self._paths:
             self._paths[key] = self._paths.pop(key)          # most recently used last
         else:
@@ -510,11 +511,12 @@ class detector(nn.Module):
             self._paths[key] = FpnRegionPath(B, dev, channels=256, n_cls=self.N_classes, pad_h=h, pad_w=w, cls_logits=True,
                                              with_rle=self.use_mask_head, box_pooled=self.roi_height, mask_pooled=14,
                                              sampling_ratio=self.roi_sampling_ratio, max_out=self.max_out,
-                                             feat_dtype=self.head_dtype or torch.float32)
+                                             feat_dtype=self.head_dtype or torch.float32, det_options=det_options)
         return self._paths[key]
 
     @torch.no_grad()
-    def forward_batched(self, images, scaling_factor, im_size, blob_hw=None):
+    def forward_batched(self, images, scaling_factor, im_size, blob_hw=None, do_soft_nms=False, soft_nms_sigma=0.5,
+                        soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8):
         """Mask / Faster R-CNN FPN forward for a BATCH (lib/model/detector.py:233-286 + :99-112 + eval_mask_FPN.ipynb:231-262,
         which the reference runs image by image with 21 synchronising copies each).
           images [B,3,H,W] prepared blobs of one padded size (utils.blob.im_list_to_blob); scaling_factor [B]; im_size [B,2]
@@ -522,6 +524,8 @@ class detector(nn.Module):
           resized size rounded up to the stride 32 (hip.prep_images' sizes); the RPN of image b then clips, filters and ranks
           exactly as a batch-1 run on that blob would (dtc_rpn_topk_decode_sized; RoIAlign still reads the padded maps).  None:
           every image is the whole blob.
+          do_soft_nms / soft_nms_sigma / soft_nms_method / do_bbox_vote / bbox_vote_thresh: the reference's test-time options of
+          box_results_with_nms_and_limit (result_utils.py:96-168, 'ID' vote scoring), run inside launch_detections.
         Everything stays on the device:  backbone(B) -> RPN heads -> FpnRegionPath.launch_proposals (top-k, NMS, collect,
         distribute, RoIAlign 7x7 in visiting order) -> fc6/fc7/cls/bbox -> launch_detections (softmax folded in, class decode,
         80-class NMS, top-100, mask-branch RoIAlign 14x14) -> mask head convs -> launch_masks (paste, binarise, COCO RLE).
@@ -545,7 +549,11 @@ class detector(nn.Module):
         if low:      # every level in the autocast type (a level left in float32 by an op outside autocast's list would mix dtypes)
             feats = [f.to(self.backbone_dtype) for f in feats]
             img_features = feats
-        path = self._region_path(B, h, w, dev)
+        det_options = None
+        if do_soft_nms or do_bbox_vote:
+            det_options = dict(do_soft_nms=bool(do_soft_nms), soft_nms_sigma=float(soft_nms_sigma), soft_nms_method=soft_nms_method,
+                               do_bbox_vote=bool(do_bbox_vote), bbox_vote_thresh=float(bbox_vote_thresh))
+        path = self._region_path(B, h, w, dev, det_options)
         path.bind_rpn([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox], feats,
                       scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
         path.launch_proposals()

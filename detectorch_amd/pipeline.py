@@ -33,8 +33,11 @@ class FpnRegionPath:
                  collect_top_n=1000, rpn_nms_thresh=0.7, max_det=100, max_out=128, mask_res=28,
                  box_pooled=7, mask_pooled=14, sampling_ratio=2, pad_h=synth.FPN_PAD_H, pad_w=synth.FPN_PAD_W,
                  feat_dtype=torch.float32, crop_capacity=8 << 20, cls_logits=False, with_rle=False,
-                 rle_runs_stride=4096, rle_str_stride=8192):
+                 rle_runs_stride=4096, rle_str_stride=8192, det_options=None):
+        """det_options: dict of the reference's test-time options of box_results_with_nms_and_limit (do_soft_nms, soft_nms_sigma,
+        soft_nms_method, do_bbox_vote, bbox_vote_thresh; hip.det_options), baked into the detection launch; None: hard NMS."""
         self.B, self.dev = batch, device
+        self.det_opt = hip.det_options(**(det_options or {}))
         self.with_rle, self.rle_runs_stride, self.rle_str_stride = with_rle, int(rle_runs_stride), int(rle_str_stride)
         self.cls_logits = cls_logits       # bind() receives the cls_score layer's raw output; softmax folded into the kernel
         self.C, self.n_cls = channels, n_cls
@@ -76,7 +79,7 @@ class FpnRegionPath:
         D = self.max_out
         self.dets, self.det_roi = torch.zeros((B, D, 6), device=dev), torch.zeros((B, D), dtype=i32, device=dev)
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
-        self.det_ws = hip.workspace(L.dtc_postprocess_detections_workspace_bytes(B, T, self.n_cls), dev)
+        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, self.n_cls, self.det_opt), dev)
         self.det_count_c = e(B, 1, dtype=i32)
         self.m_rois5, self.m_levels, self.m_n = e(B, D, 5), e(B, D, dtype=i32), e(B, dtype=i32)
         self.m_by_level, self.m_level_counts, self.m_restore = e(B, D, 4), e(B, 4, dtype=i32), e(B, D, dtype=i32)
@@ -184,22 +187,17 @@ class FpnRegionPath:
         L, B, ck = hip.lib(), self.B, hip.check
         st = st or hip.stream_ptr(self.dev)
         T, D = self.top_n, self.max_out
+        # one entry for both forms (dtc_postprocess_detections_ex): with the fused mask-branch mapping (fpn != NULL), or without
+        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
+                                           1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
+                                           self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
+                                           self.det_opt, self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
+                                           self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D,
+                                           self.m_map if self.fused_mask_map else None, st),
+           "postprocess_detections_ex")
         if self.fused_mask_map:
-            ck(L.dtc_postprocess_detections_fpn(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
-                                                1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), self.sf.data_ptr(),
-                                                self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
-                                                self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(), self.det_roi.data_ptr(),
-                                                self.det_scaled.data_ptr(), self.det_count.data_ptr(), D, self.m_map, st),
-               "postprocess_detections_fpn")
             self._roi_align_mask(st)
             return
-        post = L.dtc_postprocess_detections_logits if self.cls_logits else L.dtc_postprocess_detections
-        ck(post(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
-                self.bbox_pred.data_ptr(), self.sf.data_ptr(), self.im_size.data_ptr(), B, T,
-                self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
-                self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
-                self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D, st),
-           "postprocess_detections")
         # mask branch: level ids of the (scaled) detection boxes, multilevel_rois.py:19-39
         ck(L.dtc_fpn_collect_distribute(self.det_scaled.data_ptr(), None, self.det_count.data_ptr(), B, 1, D, D, 2, 5,
                                         self.m_rois5.data_ptr(), None, self.m_levels.data_ptr(), self.m_n.data_ptr(),
@@ -304,8 +302,10 @@ class C4RegionPath:
 
     def __init__(self, batch, device, channels=1024, n_cls=81, pre_nms_top_n=6000, post_nms_top_n=1000, rpn_nms_thresh=0.7,
                  pooled=7, sampling_ratio=0, max_det=100, max_out=128, im_h=synth.IM_H, im_w=synth.IM_W,
-                 feat_dtype=torch.float32):
+                 feat_dtype=torch.float32, det_options=None):
+        """det_options: as FpnRegionPath's (the reference's Soft-NMS / bbox-vote options; None: hard NMS)."""
         self.B, self.dev, self.C, self.n_cls = batch, device, channels, n_cls
+        self.det_opt = hip.det_options(**(det_options or {}))
         self.pre, self.post, self.top_n = pre_nms_top_n, post_nms_top_n, post_nms_top_n
         self.thresh, self.pooled, self.sr = rpn_nms_thresh, pooled, sampling_ratio
         self.max_det, self.max_out, self.im_h, self.im_w = max_det, max_out, im_h, im_w
@@ -333,7 +333,7 @@ class C4RegionPath:
         D = max_out
         self.dets, self.det_roi = torch.zeros((B, D, 6), device=dev), torch.zeros((B, D), dtype=i32, device=dev)
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
-        self.det_ws = hip.workspace(L.dtc_postprocess_detections_workspace_bytes(B, T, n_cls), dev)
+        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, n_cls, self.det_opt), dev)
 
     def bind(self, rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, scaling_factor, im_size, im_hw=None):
         """im_hw [B,2]: each image's own size inside the padded batch, kept in self.rpn_im_hw (see FpnRegionPath.bind_rpn)."""
@@ -365,12 +365,13 @@ class C4RegionPath:
                                         self.level_counts.data_ptr(), self.idx_restore.data_ptr(),
                                         self.roi_order.data_ptr(), self.roi_desc.data_ptr(), 1, st), "collect")
         self._roi_align_box(st)
-        ck(L.dtc_postprocess_detections(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
-                                        self.bbox_pred.data_ptr(), self.sf.data_ptr(), self.im_size.data_ptr(), B, T,
-                                        self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
-                                        self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
-                                        self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D, st),
-           "postprocess_detections")
+        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(), 0,
+                                           self.bbox_pred.data_ptr(), None, self.sf.data_ptr(), self.im_size.data_ptr(), B, T,
+                                           self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det, self.det_opt,
+                                           self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
+                                           self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D,
+                                           None, st),
+           "postprocess_detections_ex")
 
     def _roi_align_box(self, st=None):
         st = st or hip.stream_ptr(self.dev)

@@ -287,6 +287,48 @@ int dtc_box_results_nms_limit(const float* scores, const float* boxes, const int
                               size_t workspace_bytes, float* dets, int32_t* det_roi, int32_t* det_count, int max_out,
                               dtc_stream_t stream);
 
+/* The reference's two optional test-time branches of box_results_with_nms_and_limit (lib/utils/result_utils.py:96-168),
+ * Detectron's TEST.SOFT_NMS and TEST.BBOX_VOTE, on the batched device path.
+ *   nms_method         0: cython_nms.nms (hard NMS, the other entries' behaviour); Soft-NMS (cython_nms.soft_nms,
+ *                      :133-140): 1 linear, 2 gaussian, 3 hard.  Nt = nms_thresh.
+ *   soft_sigma         gaussian sigma (0.5, :101); must be > 0 with method 2.
+ *   soft_score_thresh  score floor of the Soft-NMS walk (0.0001, :138): a row decayed below it is discarded.
+ *   bbox_vote          0/1: box_voting(nms_dets, dets_j, bbox_vote_thresh, 'ID') (:145-151); bbox_vote_thresh in (0, 1] (0.8).
+ * Semantics: Soft-NMS works on dets_j in candidate order (roi ascending, :127-132); its rows of a class come out in selection
+ * order with their DECAYED scores, which the max_det limit (:154-163, ties kept) uses.  Voting refines the post-NMS rows against
+ * ALL of the class's candidates (undecayed weights); 'ID' scoring leaves the score.  Hard NMS keeps the roi-ascending order. */
+typedef struct dtc_det_options {
+  int32_t nms_method;
+  float soft_sigma;
+  float soft_score_thresh;
+  int32_t bbox_vote;
+  float bbox_vote_thresh;
+} dtc_det_options;
+
+/* Workspace of dtc_postprocess_detections_ex; opt == NULL (or hard NMS without voting): == dtc_postprocess_detections_workspace_bytes.
+ * 0 for invalid arguments. */
+size_t dtc_postprocess_detections_ex_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt);
+
+/* One entry for every form of the batched detection post-processing, with the options above:
+ *   probabilities or logits (scores_are_logits, as dtc_postprocess_detections[_logits]); decoded_boxes [B,R,4*n_cls] already
+ *   decoded + clipped boxes (as dtc_box_results_nms_limit: rois5 / bbox_pred / scaling_factor / im_size unused, det_rois_scaled
+ *   must be NULL) or NULL (decode from rois5 + bbox_pred); fpn: the fused mask-branch mapping of dtc_postprocess_detections_fpn,
+ *   or NULL.  opt == NULL, or nms_method 0 without voting: bit-identical to those entries (same launches).
+ * Outputs as dtc_postprocess_detections; with Soft-NMS the rows of a class are in selection order and carry the decayed score;
+ * with voting dets[:, :4] and det_rois_scaled hold the voted boxes, and the fpn mapping is computed from them.
+ * DTC_EINVAL: an unknown nms_method, soft_sigma <= 0 with gaussian, bbox_vote not 0/1, bbox_vote_thresh outside (0, 1], and the
+ * argument errors of the other entries.  R <= 4096 (DTC_EUNSUPPORTED beyond), n_cls - 1 <= 256.
+ * Launches (fixed per option set, graph-capturable): the hard path's, + one per Soft-NMS (one wave per class and image: the
+ * reference's sequential walk, O(n^2) in the class's candidates), + one for voting (one wave per emitted row), + one more with
+ * voting AND fpn (the mapping of the voted boxes). */
+int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
+                                  const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor,
+                                  const float* im_size, int batch, int max_rois, int n_cls, float wx, float wy, float ww,
+                                  float wh, float score_thresh, float nms_thresh, int max_det, const dtc_det_options* opt,
+                                  void* workspace, size_t workspace_bytes, float* dets, int32_t* det_roi,
+                                  float* det_rois_scaled, int32_t* det_count, int max_out, const dtc_fpn_map_out* fpn,
+                                  dtc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * A9  Mask resize + binarise (+ paste geometry)
  * --------------------------------------------------------------------------------------------------------------- */
