@@ -271,14 +271,16 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
 }
 
 // generate_proposals.py:165-214 (weights (1,1,1,1)) + :216-238 + :151-163
-__device__ __forceinline__ float clip1(float v, float hi) { v = fminf(v, hi); return fmaxf(v, 0.f); }
+// torch.min / torch.max propagate NaN (fminf / fmaxf would return the other operand): the compares below are false on NaN, so a
+// NaN delta gives a NaN box, which fails filter_boxes (:159-162) as it does in the reference.  -0 clips to +0, as oracle.c does.
+__device__ __forceinline__ float clip1(float v, float hi) { v = v >= hi ? hi : v; return v <= 0.f ? 0.f : v; }
 
 __device__ __forceinline__ void decode_box(float ax1, float ay1, float ax2, float ay2, float dx, float dy, float dw,
                                            float dh, float out[4]) {
   const float widths = ax2 - ax1 + 1.0f, heights = ay2 - ay1 + 1.0f;          // :175-176
   const float ctr_x = ax1 + 0.5f * widths, ctr_y = ay1 + 0.5f * heights;      // :177-178
   const float clipv = 4.135166556742356f;                                     // :165 log(1000/16) as float32
-  dw = fminf(dw, clipv); dh = fminf(dh, clipv);                               // :191-192
+  dw = dw >= clipv ? clipv : dw; dh = dh >= clipv ? clipv : dh;               // :191-192 (NaN stays NaN)
   const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;          // :194-195
   const float pw = fexp_cr(dw) * widths, ph = fexp_cr(dh) * heights;          // :196-197
   out[0] = pcx - 0.5f * pw; out[1] = pcy - 0.5f * ph;                         // :201-203
