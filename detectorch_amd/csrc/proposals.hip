@@ -23,6 +23,7 @@
 #include "block_sort.h"
 #include "dtc_common.h"
 #include "radix_select.h"
+#include <stdlib.h>
 
 namespace dtc {
 DTC_PT_TABLE(proposals)
@@ -597,7 +598,9 @@ DTC_API int dtc_rpn_topk_decode_sized(const dtc_rpn_level* levels, int n_levels,
   p.ticket = reinterpret_cast<uint32_t*>(w + plan.off_ticket);
   p.blk_cnt = reinterpret_cast<uint32_t*>(w + plan.off_blk);
   p.dec_blocks = plan.dec_blocks;
-  p.resident = (long long)plan.dec_blocks * plan.n_seg <= 1024 ? 1 : 0;     // 256 CUs hold >= 4 workgroups of 256 threads each
+  // A/B knob DTC_RPN_DECODE_TICKETS=1 (tools/AB_KNOBS.md): always take run-time tickets, which never rely on co-residency
+  static const bool force_tickets = [] { const char* e = getenv("DTC_RPN_DECODE_TICKETS"); return e && atoi(e) != 0; }();
+  p.resident = !force_tickets && (long long)plan.dec_blocks * plan.n_seg <= 1024 ? 1 : 0;     // 256 CUs hold >= 4 workgroups of 256 threads each
   p.out_boxes = out_boxes; p.out_scores = out_scores; p.out_counts = out_counts;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // histograms + counters + tickets + block counts are contiguous at the start of the workspace

@@ -72,7 +72,7 @@ int dtc_roi_align_forward_ordered(const dtc_feat_level* levels, int n_levels, in
                                   dtc_stream_t stream);
 
 /* Same, driven by packed descriptors: roi_desc float32 [R,8] = (batch, x1, y1, x2, y2, level, output_row, 0), one row per
- * workgroup in visiting order (level < 0: padding row, its output row is zero-filled).  Saves the three dependent global
+ * workgroup in visiting order (level < 0: padding row, its output row is zero-filled on every call).  Saves the three dependent global
  * loads (order -> level -> roi) at the head of every workgroup.
  * Kernel selection (all produce bit-identical results): sampling_ratio 2 on NCHW maps -> cluster-stationary kernel; ONE level
  * whose whole map of 8 channels fits LDS (H*W <= ~4900 pixels: the C4 heads) with any other sampling ratio -> map-stationary
@@ -87,7 +87,8 @@ int dtc_roi_align_forward_packed(const dtc_feat_level* levels, int n_levels, int
  * lets the map-stationary kernel (the C4 heads) form everything about a RoI that does not depend on the channels -- scaled box,
  * bin sizes, adaptive grid, the axis samples of lib/cppcuda_cffi/src/cpp/roi_align_cpu_loop.cpp:36-95 -- ONCE per launch in a
  * preparation kernel instead of once per (RoI, 8-channel workgroup).  Same results bit for bit; configurations that do not
- * take that kernel ignore the workspace (NULL is allowed: then this IS dtc_roi_align_forward_packed). */
+ * take that kernel ignore the workspace (NULL is allowed: then this IS dtc_roi_align_forward_packed).  The workspace needs no
+ * clearing: every call rewrites the records it reads, whatever another call over another RoI set left there. */
 size_t dtc_roi_align_workspace_bytes(int n_rois);
 
 /* Exactness switch of the adaptive-sampling (sampling_ratio <= 0) single-level path.  SEMANTICS: one process-wide value shared by
@@ -175,13 +176,15 @@ int dtc_rpn_topk_decode(const dtc_rpn_level* levels, int n_levels, int batch, fl
  * y < ceil(h_b / feat_stride), x < ceil(w_b / feat_stride) take part, the per-segment top-n is min(pre_nms_top_n, A * H_b * W_b),
  * boxes are clipped to (w_b - 1, h_b - 1) and centre-filtered against (w_b, h_b).  Ties keep the ascending (h,w,a) order (row-major
  * order survives the crop).  Sizes above (im_h, im_w) are clamped to it and the cell extent to the map; h_b <= 0 or w_b <= 0 gives
- * count 0.  The level maps, k_stride and the workspace are those of the padded batch. */
+ * count 0.  The level maps, k_stride and the workspace are those of the padded batch.
+ * Rows past the count (both entries): out_boxes / out_scores rows >= out_counts[s] are unspecified (they may hold a previous call's
+ * values); out_counts is rewritten on every call.  Anchor cells outside an image's extent are never read for that image's output. */
 int dtc_rpn_topk_decode_sized(const dtc_rpn_level* levels, int n_levels, int batch, float im_h, float im_w, const float* im_hw,
                               float min_size_scaled, void* workspace, size_t workspace_bytes, float* out_boxes,
                               float* out_scores, int32_t* out_counts, int k_stride, dtc_stream_t stream);
 
 /* proposals[keep] / scores[keep] of generate_proposals.py:119-120 for every segment: out_boxes [n_seg, keep_stride, 4],
- * out_scores [n_seg, keep_stride] (rows >= keep_count[s] untouched). */
+ * out_scores [n_seg, keep_stride] (rows >= keep_count[s] untouched: they keep whatever the buffer held). */
 int dtc_gather_kept(const float* sorted_boxes, const float* sorted_scores, int n_seg, int k_stride, const int32_t* keep,
                     const int32_t* keep_count, int keep_stride, float* out_boxes, float* out_scores,
                     dtc_stream_t stream);
@@ -205,7 +208,10 @@ int dtc_gather_kept(const float* sorted_boxes, const float* sorted_scores, int n
  *   roi_desc float32 [B,topN,8] (nullable) = the same rois packed in visiting order as (batch,x1,y1,x2,y2,level,row,0) for
  *   dtc_roi_align_forward_packed.
  * inputs_sorted != 0 promises that every input list is already in descending score order (true for NMS output): the
- * lists are then merged by rank instead of sorted. */
+ * lists are then merged by rank instead of sorted.
+ * Rewritten on every call, whatever the previous call left: n_out, level_counts, roi_levels (all topN rows: -1 past n_out),
+ * roi_order (all topN rows: a permutation of b*topN + [0, topN)) and roi_desc (all topN rows: padding rows carry level -1, so
+ * RoIAlign zero-fills their output rows).  Rows >= n_out[b] of rois5, roi_scores, rois_by_level and idx_restore are unspecified. */
 int dtc_fpn_collect_distribute(const float* in_boxes, const float* in_scores, const int32_t* in_counts, int batch,
                                int n_in_levels, int in_stride, int post_nms_top_n, int k_min, int k_max, float* rois5,
                                float* roi_scores, int32_t* roi_levels, int32_t* n_out, float* rois_by_level,
@@ -238,7 +244,11 @@ int dtc_fpn_collect_distribute_kept(const float* sorted_boxes, const float* sort
  * ties like the reference, :161; rows beyond max_out are dropped -- compare det_count with max_out). R <= 4096.
  * Cost model: the per-class NMS of a (class, image) segment runs inside ONE workgroup, n^2 / 2 pair tests for n candidates above the
  * score threshold -- microseconds for the 81-class heads this serves (tens of candidates per class), ~100 us at n = 1000, ~1.5 ms at
- * n = 4096: few-class models with low thresholds should expect the largest class segment to set the launch time. */
+ * n = 4096: few-class models with low thresholds should expect the largest class segment to set the launch time.
+ * Input rows r in [n_rois[b], R) of cls_score / bbox_pred must be addressable (the candidate scan loads them before it knows the
+ * count) and may hold any bits, NaN included: they never reach an output.  Outputs: det_count is rewritten on every call; rows
+ * d >= min(det_count[b], max_out) of dets / det_roi / det_rois_scaled are unspecified (they may hold a previous call's rows).
+ * The same holds for every detection entry below. */
 size_t dtc_postprocess_detections_workspace_bytes(int batch, int max_rois, int n_cls);
 int dtc_postprocess_detections(const float* rois5, const int32_t* n_rois, const float* cls_score, const float* bbox_pred,
                                const float* scaling_factor, const float* im_size, int batch, int max_rois, int n_cls,
@@ -263,7 +273,8 @@ int dtc_postprocess_detections_logits(const float* rois5, const int32_t* n_rois,
  * dtc_fpn_collect_distribute(det_rois_scaled, in_scores = NULL, det_count, batch, 1, max_out, max_out, k_min, k_max, ...) would
  * write, bit for bit, without that launch (the workgroup that finalises an image's detections has its <= ~100 rows in hand).
  * All of fpn's pointers are [B, max_out, ...] buffers as documented at dtc_fpn_collect_distribute (roi_order / roi_desc nullable);
- * det_rois_scaled is required; max_out <= 512 (DTC_EUNSUPPORTED beyond: use the separate call). */
+ * det_rois_scaled is required; max_out <= 512 (DTC_EUNSUPPORTED beyond: use the separate call).  The fpn outputs are rewritten as
+ * dtc_fpn_collect_distribute's: n_out = min(det_count, max_out), roi_levels -1 on every row past it, roi_desc padding rows level -1. */
 typedef struct dtc_fpn_map_out {
   float* rois5; int32_t* roi_levels; int32_t* n_out; float* rois_by_level; int32_t* level_counts; int32_t* idx_restore;
   int32_t* roi_order; float* roi_desc;
@@ -339,7 +350,9 @@ int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_rois, con
  * Outputs: mask_boxes int32 [B,max_out,4] expanded+truncated ref box (:183-184); mask_rects int32 [B,max_out,4] paste
  * rectangle (x_0,y_0,x_1,y_1) (:204-207); crops uint8 [B,per_image_capacity]: for detection d the binarised resized mask
  * restricted to its paste rectangle, row-major, at byte mask_offsets[b,d] of image b's region; mask_bytes int64 [B] =
- * bytes image b needs (if > per_image_capacity the detections that did not fit were skipped). */
+ * bytes image b needs (if > per_image_capacity the detections that did not fit were skipped).  mask_bytes is rewritten on every
+ * call; rows d >= min(det_count[b], max_out) of mask_boxes / mask_rects / mask_offsets and the crop bytes outside the pasted
+ * rectangles are unspecified.  masks rows of detections d >= min(det_count[b], max_out) are never read. */
 int dtc_mask_paste(const float* masks, const int32_t* mask_index, int n_cls, int M, const float* dets,
                    const int32_t* det_count, const float* im_size, int batch, int max_out, float thresh_binarize,
                    int cls_specific_mask, uint8_t* crops, long long per_image_capacity, int32_t* mask_boxes,
@@ -352,7 +365,8 @@ int dtc_mask_paste(const float* masks, const int32_t* mask_index, int n_cls, int
  *   rle_str    uint8  [B,max_out,str_stride]   the compressed "counts" string (ASCII, no terminator), rle_str_len int32
  * A detection whose runs (string) do not fit gets rle_n_runs = -(runs needed) (rle_str_len = -(bytes needed)) and no
  * valid data: re-run with larger strides or encode that one on the host.  A detection whose crop did not fit
- * per_image_capacity (dtc_mask_paste skipped it: mask_bytes[b] > capacity) gets -1 / -1.  d >= det_count[b]: 0 / 0. */
+ * per_image_capacity (dtc_mask_paste skipped it: mask_bytes[b] > capacity) gets -1 / -1.  d >= det_count[b]: 0 / 0, rewritten on
+ * every call.  rle_counts / rle_str past each row's length are unspecified. */
 int dtc_mask_rle(const uint8_t* crops, long long per_image_capacity, const int32_t* mask_rects,
                  const long long* mask_offsets, const int32_t* det_count, const float* im_size, int batch, int max_out,
                  uint32_t* rle_counts, int runs_stride, int32_t* rle_n_runs, uint8_t* rle_str, int str_stride,
