@@ -114,6 +114,10 @@ def lib():
     L.dtc_fpn_collect_distribute.argtypes = [p, p, p, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, i, p]
     L.dtc_fpn_collect_distribute_kept.argtypes = [p, p, i, p, p, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, p]
     L.dtc_fpn_collect_distribute_kept.restype = i
+    L.dtc_prepare_proposals_workspace_bytes.argtypes = [i, i]
+    L.dtc_prepare_proposals_workspace_bytes.restype = sz
+    L.dtc_prepare_proposals.argtypes = [p, p, p, i, i, f, i, i, i, p, sz, p, p, p, p, p, p, p, p, p, p]
+    L.dtc_prepare_proposals.restype = i
     L.dtc_roi_align_forward_packed.argtypes = [C.POINTER(FeatLevel), i, i, i, p, i, i, i, i, p, i, p]
     L.dtc_roi_align_forward_packed.restype = i
     L.dtc_roi_align_workspace_bytes.argtypes = [i]
@@ -434,6 +438,40 @@ def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max
                                               out["idx_restore"].data_ptr(), out["roi_order"].data_ptr(),
                                               out["roi_desc"].data_ptr(), 1 if inputs_sorted else 0, stream_ptr(dev))
     check(rc, "dtc_fpn_collect_distribute")
+    return out
+
+
+def prepare_proposals(boxes, counts, im_scale, dedup_scale=0.0625, k_min=2, k_max=5, max_out=None, out=None, ws=None):
+    """dtc_prepare_proposals: precomputed proposals -> the outputs of fpn_collect_distribute (in_scores = NULL), one call for a batch.
+    boxes float32 [B,N,4] in original-image coordinates, counts int32 [B] (rows past them ignored), im_scale [B] (rounded to
+    float32 like numpy's float32-array * Python-float product); dedup_scale 0.0625 (remove_dup_prop) or 0 (keep every row in input
+    order); k_min == k_max: one level (C4).  -> dict(rois5 [B,T,5], roi_levels [B,T], n_out [B], rois_by_level [B,T,4],
+    level_counts [B,nl], idx_restore [B,T], roi_order [B,T], roi_desc [B,T,8], src_index [B,T]) with T = max_out (default N).
+    out / ws: preallocated dict / workspace to write into (graph capture)."""
+    dev = _require_cuda(boxes, counts)
+    boxes = boxes.contiguous()
+    B, N = boxes.shape[0], boxes.shape[1]
+    T = int(max_out or N)
+    nl = k_max - k_min + 1
+    f32, i32 = torch.float32, torch.int32
+    if out is None:
+        out = dict(rois5=torch.empty((B, T, 5), dtype=f32, device=dev), roi_levels=torch.empty((B, T), dtype=i32, device=dev),
+                   n_out=torch.empty((B,), dtype=i32, device=dev), rois_by_level=torch.empty((B, T, 4), dtype=f32, device=dev),
+                   level_counts=torch.empty((B, nl), dtype=i32, device=dev), idx_restore=torch.empty((B, T), dtype=i32, device=dev),
+                   roi_order=torch.empty((B, T), dtype=i32, device=dev), roi_desc=torch.empty((B, T, 8), dtype=f32, device=dev),
+                   src_index=torch.empty((B, T), dtype=i32, device=dev))
+    counts = counts.to(i32).contiguous()
+    im_scale = torch.as_tensor(im_scale, dtype=f32).to(dev).reshape(B).contiguous()
+    L = lib()
+    if ws is None:
+        ws = workspace(L.dtc_prepare_proposals_workspace_bytes(B, T), dev)
+    with torch.cuda.device(dev):
+        rc = L.dtc_prepare_proposals(boxes.data_ptr(), counts.data_ptr(), im_scale.data_ptr(), B, N, float(dedup_scale), k_min, k_max,
+                                     T, ws.data_ptr(), ws.numel(), out["rois5"].data_ptr(), out["roi_levels"].data_ptr(),
+                                     out["n_out"].data_ptr(), out["rois_by_level"].data_ptr(), out["level_counts"].data_ptr(),
+                                     out["idx_restore"].data_ptr(), out["roi_order"].data_ptr(), out["roi_desc"].data_ptr(),
+                                     _ptr(out.get("src_index")), stream_ptr(dev))
+    check(rc, "dtc_prepare_proposals")
     return out
 
 

@@ -496,10 +496,10 @@ class detector(nn.Module):
         return super().load_state_dict(*args, **kw)
 
     # ---- batched entry: B images, zero host round trips ------------------------------------------------------------------
-    def _region_path(self, B, h, w, dev, det_options=None):
-        from ..pipeline import FpnRegionPath
+    def _region_path(self, B, h, w, dev, det_options=None, top_n=1000):
+        from ..pipeline import C4RegionPath, FpnRegionPath
         # the detection options are baked into the path's launches (and its captured graph): part of the key
-        key = (B, h, w, str(dev), self.max_out, tuple(sorted((det_options or {}).items())))
+        key = (B, h, w, str(dev), self.max_out, tuple(sorted((det_options or {}).items())), top_n)
         if key in self._paths:
             self._paths[key] = self._paths.pop(key)          # most recently used last
         else:
@@ -508,15 +508,85 @@ class detector(nn.Module):
             # next forward_batched call with the same (B, h, w) -- copy what has to outlive that call.
             while len(self._paths) >= self.max_cached_paths:
                 self._paths.pop(next(iter(self._paths)))
-            self._paths[key] = FpnRegionPath(B, dev, channels=256, n_cls=self.N_classes, pad_h=h, pad_w=w, cls_logits=True,
-                                             with_rle=self.use_mask_head, box_pooled=self.roi_height, mask_pooled=14,
-                                             sampling_ratio=self.roi_sampling_ratio, max_out=self.max_out,
-                                             feat_dtype=self.head_dtype or torch.float32, det_options=det_options)
+            if not self.use_fpn_body:
+                # C4: RPN parameters of the model's own proposal generator (6000 / 1000 / 0.7), RoIAlign roi_height x roi_width on
+                # res4 with the model's sampling ratio (0: adaptive), mask branch 14x14 -> M = 14
+                g = getattr(self, "proposal_generator", None)
+                kw = {} if g is None else dict(pre_nms_top_n=g.rpn_pre_nms_top_n, rpn_nms_thresh=g.rpn_nms_thresh)
+                self._paths[key] = C4RegionPath(B, dev, channels=self.model.layer3[-1].conv3.out_channels, n_cls=self.N_classes,
+                                                post_nms_top_n=top_n if g is None else g.rpn_post_nms_top_n, pooled=self.roi_height,
+                                                sampling_ratio=self.roi_sampling_ratio, max_out=self.max_out, im_h=h, im_w=w,
+                                                det_options=det_options, cls_logits=True, with_masks=self.use_mask_head,
+                                                mask_res=14, with_rle=self.use_mask_head, **kw)
+            else:
+                self._paths[key] = FpnRegionPath(B, dev, channels=256, n_cls=self.N_classes, pad_h=h, pad_w=w, cls_logits=True,
+                                                 with_rle=self.use_mask_head, box_pooled=self.roi_height, mask_pooled=14,
+                                                 sampling_ratio=self.roi_sampling_ratio, max_out=self.max_out,
+                                                 feat_dtype=self.head_dtype or torch.float32, det_options=det_options,
+                                                 collect_top_n=top_n)
         return self._paths[key]
+
+    @staticmethod
+    def _proposal_inputs(proposals, proposal_counts, B, dev):
+        """proposals [B,N,4] (or a list of B [n_b,4] arrays) + counts -> (float32 [B,N,4], int32 [B]) on the device"""
+        if isinstance(proposals, (list, tuple)):
+            rows = [torch.as_tensor(p, dtype=torch.float32).reshape(-1, 4) for p in proposals]
+            N = max(1, max(int(r.shape[0]) for r in rows))
+            p = torch.zeros((len(rows), N, 4), dtype=torch.float32)
+            for b, r in enumerate(rows):
+                p[b, :r.shape[0]] = r
+            if proposal_counts is None:
+                proposal_counts = [int(r.shape[0]) for r in rows]
+            proposals = p
+        proposals = torch.as_tensor(proposals).to(device=dev, dtype=torch.float32).contiguous()
+        if proposals.dim() != 3 or proposals.shape[0] != B or proposals.shape[2] != 4:
+            raise ValueError("proposals must be [B, N, 4] in original-image coordinates")
+        if proposal_counts is None:
+            proposal_counts = [proposals.shape[1]] * B
+        counts = torch.as_tensor(proposal_counts).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+        return proposals, counts
+
+    @torch.no_grad()
+    def _forward_batched_c4(self, images, sf, sz, blob_hw, det_options, proposals, proposal_counts):
+        """C4 models (e2e Faster / Mask R-CNN R-50-C4, Fast R-CNN R-50-C4): res4 -> C4RegionPath stages -> res5 head -> detections
+        -> shared res5 + deconv + classifier -> paste (M = 14) + RLE."""
+        if (getattr(self, "_opt_dtype", None) is not None or self.channels_last or self.backbone_dtype not in (None, torch.float32)
+                or self.head_dtype not in (None, torch.float32)):
+            raise NotImplementedError("forward_batched runs the C4 configurations in float32 NCHW (no optimize_for_inference, "
+                                      "16-bit or channels_last)")
+        B, h, w = images.size(0), images.size(2), images.size(3)
+        dev = images.device
+        img_features = self.conv_body(images)                                       # res4 [B, 1024, h/16, w/16]
+        top_n = 1000
+        if proposals is not None:
+            props, counts = self._proposal_inputs(proposals, proposal_counts, B, dev)
+            top_n = int(props.shape[1])
+        else:
+            rpn_cls, rpn_bbox = self.rpn(img_features, logits=self.fuse_rpn_sigmoid)
+        path = self._region_path(B, h, w, dev, det_options, top_n)
+        if proposals is not None:
+            path.bind_proposals(props, counts, sf, img_features)
+        else:
+            path.bind_rpn_outputs(rpn_cls.float().contiguous(), rpn_bbox.float().contiguous(), img_features,
+                          scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
+        path.launch_proposals()
+        x = self._head(path.box_feats)                                              # res5 + avgpool: [B*T, 2048]
+        T = path.top_n
+        cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
+        bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
+        path.bind_heads(cls_logits, bbox_pred, sf, sz)
+        path.launch_detections()
+        path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
+        if self.use_mask_head:
+            mh = self.mask_head                                                     # detector.py:99-112, the non-FPN branch
+            m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(path.mask_feats))))
+            path.bind_masks((torch.sigmoid(m) if mh.output_prob else m).contiguous())        # [B*max_out, 81, 14, 14]
+            path.launch_masks()
+        return path
 
     @torch.no_grad()
     def forward_batched(self, images, scaling_factor, im_size, blob_hw=None, do_soft_nms=False, soft_nms_sigma=0.5,
-                        soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8):
+                        soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8, proposals=None, proposal_counts=None):
         """Mask / Faster R-CNN FPN forward for a BATCH (lib/model/detector.py:233-286 + :99-112 + eval_mask_FPN.ipynb:231-262,
         which the reference runs image by image with 21 synchronising copies each).
           images [B,3,H,W] prepared blobs of one padded size (utils.blob.im_list_to_blob); scaling_factor [B]; im_size [B,2]
@@ -530,11 +600,30 @@ class detector(nn.Module):
         distribute, RoIAlign 7x7 in visiting order) -> fc6/fc7/cls/bbox -> launch_detections (softmax folded in, class decode,
         80-class NMS, top-100, mask-branch RoIAlign 14x14) -> mask head convs -> launch_masks (paste, binarise, COCO RLE).
         Returns the FpnRegionPath holding the fixed-shape device results (dets [B,128,6], det_count [B], rois5 [B,1000,5],
-        n_rois [B], crops / RLE strings ...) plus the head outputs; `per_image(b)` gives the reference's forward() tuple."""
-        if not (self.use_rpn_head and self.use_fpn_body and self.use_two_layer_mlp_head):
-            raise NotImplementedError("forward_batched covers the FPN configurations (e2e_faster/mask_rcnn_R-*-FPN)")
+        n_rois [B], crops / RLE strings ...) plus the head outputs; `per_image(b)` gives the reference's forward() tuple.
+
+        C4 models (no FPN body) run the same stages through a C4RegionPath: RPN of the model's own proposal_generator, RoIAlign
+        roi_height x roi_width on res4, the res5 conv_head, and with a mask head its 14x14 branch (paste with M = 14, RLE).
+        proposals [B,N,4] (original-image coordinates; or a list of B [n_b,4] arrays) + proposal_counts [B] (default: all N): the
+        precomputed proposals of a model WITHOUT an RPN head (Fast R-CNN C4 / FPN; required there, rejected with one).  Scaled by
+        scaling_factor, deduplicated on the 1/16 grid and distributed over the levels on the device (dtc_prepare_proposals:
+        preprocess_sample.py:35-45); N <= 2048."""
+        if self.use_rpn_head and proposals is not None:
+            raise ValueError("this model has an RPN head: its proposals come from it (proposals= is for models without one)")
+        if not self.use_rpn_head and proposals is None:
+            raise ValueError("a model without an RPN head needs precomputed proposals (proposals=)")
+        det_options = None
+        if do_soft_nms or do_bbox_vote:
+            det_options = dict(do_soft_nms=bool(do_soft_nms), soft_nms_sigma=float(soft_nms_sigma), soft_nms_method=soft_nms_method,
+                               do_bbox_vote=bool(do_bbox_vote), bbox_vote_thresh=float(bbox_vote_thresh))
         B, h, w = images.size(0), images.size(2), images.size(3)
         dev = images.device
+        sf = torch.as_tensor(scaling_factor, dtype=torch.float32, device=dev).reshape(B).contiguous()
+        sz = torch.as_tensor(im_size, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
+        if not self.use_fpn_body:
+            return self._forward_batched_c4(images, sf, sz, blob_hw, det_options, proposals, proposal_counts)
+        if not self.use_two_layer_mlp_head:
+            raise NotImplementedError("forward_batched covers the FPN configurations with the two-layer MLP head and the C4 ones")
         opt = getattr(self, "_opt_dtype", None)                 # optimize_for_inference(16-bit): weights live in that type
         # one copy at most: the blob in the body's type and layout
         images = images.to(dtype=opt or images.dtype, memory_format=torch.channels_last if self.channels_last else torch.preserve_format)
@@ -544,25 +633,25 @@ class detector(nn.Module):
         with (torch.autocast("cuda", dtype=self.backbone_dtype) if low and opt is None else contextlib.nullcontext()):
             img_features = self.conv_body(images)
             feats = list(img_features)
-            rpn_in = feats + ([F.max_pool2d(feats[-1], 1, stride=2)] if self.fpn_extra_lvl else [])
-            cls_bbox = [self.rpn(f, logits=self.fuse_rpn_sigmoid) for f in rpn_in]
+            if self.use_rpn_head:
+                rpn_in = feats + ([F.max_pool2d(feats[-1], 1, stride=2)] if self.fpn_extra_lvl else [])
+                cls_bbox = [self.rpn(f, logits=self.fuse_rpn_sigmoid) for f in rpn_in]
         if low:      # every level in the autocast type (a level left in float32 by an op outside autocast's list would mix dtypes)
             feats = [f.to(self.backbone_dtype) for f in feats]
             img_features = feats
-        det_options = None
-        if do_soft_nms or do_bbox_vote:
-            det_options = dict(do_soft_nms=bool(do_soft_nms), soft_nms_sigma=float(soft_nms_sigma), soft_nms_method=soft_nms_method,
-                               do_bbox_vote=bool(do_bbox_vote), bbox_vote_thresh=float(bbox_vote_thresh))
-        path = self._region_path(B, h, w, dev, det_options)
-        path.bind_rpn([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox], feats,
-                      scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
+        if proposals is not None:
+            props, counts = self._proposal_inputs(proposals, proposal_counts, B, dev)
+            path = self._region_path(B, h, w, dev, det_options, int(props.shape[1]))
+            path.bind_proposals(props, counts, sf, feats[:len(self.roi_spatial_scale)])
+        else:
+            path = self._region_path(B, h, w, dev, det_options)
+            path.bind_rpn([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox], feats,
+                          scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
         path.launch_proposals()
         x = self._head(path.box_feats)                                              # [B*1000, 1024]
         T = path.top_n
         cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
         bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
-        sf = torch.as_tensor(scaling_factor, dtype=torch.float32, device=dev).reshape(B).contiguous()
-        sz = torch.as_tensor(im_size, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
         path.bind_heads(cls_logits, bbox_pred, sf, sz)
         path.launch_detections()
         path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
@@ -592,8 +681,9 @@ class detector(nn.Module):
         bbox_pred [n,324], rois [n,4], img_features of that image).  Syncs (one count) -- for callers that want the
         reference's shapes; the fixed-shape tensors on `path` need no sync."""
         n = int(path.n_rois[b].item())
+        feats = path.img_features
         return (F.softmax(path.cls_logits_out[b, :n], dim=1), path.bbox_pred_out[b, :n], path.rois5[b, :n, 1:],
-                [f[b:b + 1] for f in path.img_features])
+                feats[b:b + 1] if torch.is_tensor(feats) else [f[b:b + 1] for f in feats])     # C4: one res4 tensor
 
     # ---- caffe2 / Detectron pickle import (detector.py:289-374) -------------------------------------------------------
     def load_pretrained_weights(self, caffe_pkl_file, model='detector'):

@@ -28,6 +28,45 @@ def _device_hw(im_hw, B, dev):
     return torch.as_tensor(im_hw, dtype=torch.float32).to(dev).reshape(B, 2).clone().contiguous()
 
 
+def _device_input(t, dtype, shape, dev):
+    """A bound input: the caller's tensor itself when it already is a contiguous device tensor of that type (new values copied into
+    it apply at the next step / replay), otherwise an owned copy."""
+    t = torch.as_tensor(t)
+    if t.device == torch.device(dev) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape):
+        return t
+    return t.to(device=dev, dtype=dtype).reshape(shape).contiguous().clone()
+
+
+def _bind_proposals(path, boxes, counts, im_scale, dedup_scale):
+    """Shared by FpnRegionPath / C4RegionPath.bind_proposals.  boxes float32 [B,N,4] (original-image coordinates, N <= top_n and
+    <= 2048), counts int32 [B] (rows past them are ignored), im_scale float32 [B] (the blob scale of each image).  Kept as
+    path.prop_in / prop_in_counts / prop_im_scale, which every launch (and a captured graph) reads; path.prop_src [B,T] = the input
+    row of each roi (np.unique's index)."""
+    dev, B = path.dev, path.B
+    boxes = torch.as_tensor(boxes)
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4:
+        raise ValueError("proposals must be [B, N, 4]")
+    N = int(boxes.shape[1])
+    if N < 1 or N > path.top_n or N > 2048:
+        raise ValueError("proposals per image: 1 <= N <= min(%d, 2048) (the path's roi rows), got %d" % (path.top_n, N))
+    path.prop_in = _device_input(boxes, torch.float32, (B, N, 4), dev)
+    path.prop_in_counts = _device_input(counts, torch.int32, (B,), dev)
+    path.prop_im_scale = _device_input(im_scale, torch.float32, (B,), dev)
+    path.prop_dedup = float(dedup_scale)
+    path.prop_src = torch.zeros((B, path.top_n), dtype=torch.int32, device=dev)
+    path.prep_ws = hip.workspace(hip.lib().dtc_prepare_proposals_workspace_bytes(B, path.top_n), dev)
+    path.graph = None
+
+
+def _launch_prepare(path, k_min, k_max, st):
+    hip.check(hip.lib().dtc_prepare_proposals(path.prop_in.data_ptr(), path.prop_in_counts.data_ptr(), path.prop_im_scale.data_ptr(),
+                                              path.B, path.prop_in.shape[1], path.prop_dedup, k_min, k_max, path.top_n,
+                                              path.prep_ws.data_ptr(), path.prep_ws.numel(), path.rois5.data_ptr(),
+                                              path.roi_levels.data_ptr(), path.n_rois.data_ptr(), path.rois_by_level.data_ptr(),
+                                              path.level_counts.data_ptr(), path.idx_restore.data_ptr(), path.roi_order.data_ptr(),
+                                              path.roi_desc.data_ptr(), path.prop_src.data_ptr(), st), "prepare_proposals")
+
+
 class FpnRegionPath:
     def __init__(self, batch, device, channels=256, n_cls=81, pre_nms_top_n=1000, post_nms_top_n=1000,
                  collect_top_n=1000, rpn_nms_thresh=0.7, max_det=100, max_out=128, mask_res=28,
@@ -113,6 +152,7 @@ class FpnRegionPath:
         proposals are those of a batch-1 run on that blob.  Kept in the device tensor self.rpn_im_hw, which every launch (and a
         captured graph) reads: sizes written into it in place apply to the next step.  None: every image is (pad_h, pad_w)."""
         self.rpn_cls, self.rpn_bbox, self.feats = rpn_cls, rpn_bbox, feats
+        self.prop_in = None
         self.rpn_im_hw = _device_hw(im_hw, self.B, self.dev)
         self.rpn_lv, self._alive = hip.make_rpn_levels(rpn_cls, rpn_bbox, self.anchors, self.strides, [self.pre] * 5,
                                                        scores_are_logits=scores_are_logits)
@@ -123,6 +163,16 @@ class FpnRegionPath:
         self.feat_code = hip._dtype_code(feats[0].dtype)
         self.out_code = hip._dtype_code(self.feat_dtype)
         self.graph = None
+
+    def bind_proposals(self, boxes, counts, im_scale, feats, dedup_scale=0.0625):
+        """Precomputed proposals instead of the RPN (the Fast R-CNN flows): boxes [B,N,4] in original-image coordinates, counts [B],
+        im_scale [B] (see _bind_proposals).  launch_proposals then runs dtc_prepare_proposals -- scale, remove_dup_prop,
+        add_multilevel_rois_for_test -- instead of the RPN, NMS and collect launches."""
+        self.feats = feats
+        self.feat_lv, _, _ = hip.make_levels(feats, self.roi_scales)
+        self.feat_code = hip._dtype_code(feats[0].dtype)
+        self.out_code = hip._dtype_code(self.feat_dtype)
+        _bind_proposals(self, boxes, counts, im_scale, dedup_scale)
 
     def bind_heads(self, cls_score, bbox_pred, scaling_factor, im_size):
         self.cls_score, self.bbox_pred = cls_score, bbox_pred
@@ -135,9 +185,14 @@ class FpnRegionPath:
 
     # ---- one pass of the hot path over the bound batch ---------------------------------------------------------------
     def launch_proposals(self, st=None):
-        """RPN outputs -> rois5 / level ids / visiting order -> box-head features (self.box_feats [B*T, C, 7, 7])."""
+        """RPN outputs (or bound precomputed proposals) -> rois5 / level ids / visiting order -> box-head features
+        (self.box_feats [B*T, C, 7, 7])."""
         L, B, ck = hip.lib(), self.B, hip.check
         st = st or hip.stream_ptr(self.dev)
+        if getattr(self, "prop_in", None) is not None:
+            _launch_prepare(self, 2, 5, st)
+            self._roi_align_box(st)
+            return
         S, T = B * 5, self.top_n
         ck(L.dtc_rpn_topk_decode_sized(self.rpn_lv, 5, B, float(self.pad_h), float(self.pad_w), hip._ptr(self.rpn_im_hw), 0.0,
                                        self.rpn_ws.data_ptr(), self.rpn_ws.numel(), self.pre_boxes.data_ptr(),
@@ -298,13 +353,27 @@ class C4RegionPath:
           --[roi_align on res4 [B,1024,50,84], adaptive sampling (sampling_ratio 0)]--> [B*1000,1024,P,P]               detector.py:240-248
           (res5 head + cls/bbox: convs / GEMMs, not part of the hot path -- synthetic outputs)
           --[postprocess_detections]--> dets [B,128,6]                                                                  result_utils.py:76-168
+        with_masks (Mask R-CNN C4, eval_mask.ipynb): the detection launch also maps the scaled detection boxes to one level
+          --[roi_align 14x14 on res4, sampling_ratio 0]--> mask-head features [B*128,1024,14,14]                         detector.py:99-112
+          (shared res5 + deconv + classifier: the caller)  --[mask_paste (M = mask_res), mask_rle]--> crops / COCO RLE  result_utils.py:170-220
+        bind_proposals (Fast R-CNN C4, eval_fast.ipynb): precomputed proposals --[prepare_proposals]--> rois5 replaces the RPN stages.
+    The stages can be bound and launched one by one (bind_rpn_outputs / bind_proposals -> launch_proposals -> bind_heads -> launch_detections
+    -> bind_masks -> launch_masks) by a model that runs res5 in between (detector.forward_batched).
     """
 
     def __init__(self, batch, device, channels=1024, n_cls=81, pre_nms_top_n=6000, post_nms_top_n=1000, rpn_nms_thresh=0.7,
                  pooled=7, sampling_ratio=0, max_det=100, max_out=128, im_h=synth.IM_H, im_w=synth.IM_W,
-                 feat_dtype=torch.float32, det_options=None):
-        """det_options: as FpnRegionPath's (the reference's Soft-NMS / bbox-vote options; None: hard NMS)."""
+                 feat_dtype=torch.float32, det_options=None, cls_logits=False, with_masks=False, mask_res=14, with_rle=False,
+                 crop_capacity=8 << 20, rle_runs_stride=4096, rle_str_stride=8192):
+        """det_options: as FpnRegionPath's (the reference's Soft-NMS / bbox-vote options; None: hard NMS).  cls_logits: the bound
+        cls_score is the classifier's raw output (softmax folded into the detection kernel).  with_masks: the mask branch (14x14
+        RoIAlign of the detections on res4, paste with M = mask_res, COCO RLE on the device with with_rle)."""
         self.B, self.dev, self.C, self.n_cls = batch, device, channels, n_cls
+        self.cls_logits, self.with_masks, self.M = cls_logits, with_masks, mask_res
+        self.with_rle, self.rle_runs_stride, self.rle_str_stride = with_rle, int(rle_runs_stride), int(rle_str_stride)
+        self.crop_capacity = crop_capacity
+        self.mask_p = 14
+        self.prop_in = None
         self.det_opt = hip.det_options(**(det_options or {}))
         self.pre, self.post, self.top_n = pre_nms_top_n, post_nms_top_n, post_nms_top_n
         self.thresh, self.pooled, self.sr = rpn_nms_thresh, pooled, sampling_ratio
@@ -334,21 +403,80 @@ class C4RegionPath:
         self.dets, self.det_roi = torch.zeros((B, D, 6), device=dev), torch.zeros((B, D), dtype=i32, device=dev)
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
         self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, n_cls, self.det_opt), dev)
+        if with_masks:
+            if D > 512:
+                raise ValueError("with_masks needs max_out <= 512 (the detection launch's fused level mapping)")
+            # the mask branch's rois (k_min == k_max: one level) come out of the detection launch itself
+            self.m_rois5, self.m_levels, self.m_n = e(B, D, 5), e(B, D, dtype=i32), e(B, dtype=i32)
+            self.m_by_level, self.m_level_counts, self.m_restore = e(B, D, 4), e(B, 1, dtype=i32), e(B, D, dtype=i32)
+            self.m_order, self.m_desc = e(B, D, dtype=i32), e(B, D, 8)
+            self.m_map = hip.FpnMapOut(self.m_rois5.data_ptr(), self.m_levels.data_ptr(), self.m_n.data_ptr(), self.m_by_level.data_ptr(),
+                                       self.m_level_counts.data_ptr(), self.m_restore.data_ptr(), self.m_order.data_ptr(),
+                                       self.m_desc.data_ptr(), 4, 4)
+            self.mask_feats = e(B * D, self.C, self.mask_p, self.mask_p, dtype=feat_dtype)
+            self.m_ra_ws = hip.workspace(L.dtc_roi_align_workspace_bytes(B * D), dev)
+            self.crops = torch.empty((B, crop_capacity), dtype=torch.uint8, device=dev)
+            self.mask_boxes, self.mask_rects = torch.zeros((B, D, 4), dtype=i32, device=dev), torch.zeros((B, D, 4), dtype=i32, device=dev)
+            self.mask_offsets, self.mask_bytes = torch.zeros((B, D), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev)
+            if with_rle:
+                self.rle_counts = e(B, D, self.rle_runs_stride, dtype=i32)
+                self.rle_n_runs, self.rle_str_len = torch.zeros((B, D), dtype=i32, device=dev), torch.zeros((B, D), dtype=i32, device=dev)
+                self.rle_str = torch.zeros((B, D, self.rle_str_stride), dtype=torch.uint8, device=dev)
+        self.masks = None
 
     def bind(self, rpn_cls, rpn_bbox, feat, cls_score, bbox_pred, scaling_factor, im_size, im_hw=None):
         """im_hw [B,2]: each image's own size inside the padded batch, kept in self.rpn_im_hw (see FpnRegionPath.bind_rpn)."""
+        self.bind_rpn_outputs(rpn_cls, rpn_bbox, feat, im_hw=im_hw)
+        self.bind_heads(cls_score, bbox_pred, scaling_factor, im_size)
+
+    # (not named bind_rpn: callers tell the two paths apart by FpnRegionPath's multi-level bind_rpn)
+    def bind_rpn_outputs(self, rpn_cls, rpn_bbox, feat, scores_are_logits=False, im_hw=None):
+        """The counterpart of FpnRegionPath.bind_rpn: RPN outputs [B,15,H,W] / [B,60,H,W] (scores_are_logits: pre-sigmoid) and res4
+        [B,C,H,W]."""
         self.rpn_cls, self.rpn_bbox, self.feat = rpn_cls, rpn_bbox, feat
+        self.prop_in = None
         self.rpn_im_hw = _device_hw(im_hw, self.B, self.dev)
-        self.cls_score, self.bbox_pred, self.sf, self.im_size = cls_score, bbox_pred, scaling_factor, im_size
-        self.rpn_lv, self._alive = hip.make_rpn_levels([rpn_cls], [rpn_bbox], self.anchors, [16.0], [self.pre])
+        self.rpn_lv, self._alive = hip.make_rpn_levels([rpn_cls], [rpn_bbox], self.anchors, [16.0], [self.pre],
+                                                       scores_are_logits=scores_are_logits)
         self.rpn_ws = hip.workspace(hip.lib().dtc_rpn_topk_decode_workspace_bytes(self.rpn_lv, 1, self.B, self.kmax), self.dev)
+        self._bind_feat(feat)
+
+    def _bind_feat(self, feat):
+        self.feat = feat
         self.feat_lv, _, _ = hip.make_levels([feat], [1.0 / 16.0])
         self.feat_code, self.out_code = hip._dtype_code(feat.dtype), hip._dtype_code(self.feat_dtype)
         self.graph = None
 
+    def bind_proposals(self, boxes, counts, im_scale, feat, dedup_scale=0.0625):
+        """Precomputed proposals instead of the RPN (eval_fast.ipynb): as FpnRegionPath.bind_proposals, one level (res4)."""
+        self._bind_feat(feat)
+        _bind_proposals(self, boxes, counts, im_scale, dedup_scale)
+
+    def bind_heads(self, cls_score, bbox_pred, scaling_factor, im_size):
+        self.cls_score, self.bbox_pred, self.sf, self.im_size = cls_score, bbox_pred, scaling_factor, im_size
+        self.graph = None
+
+    def bind_masks(self, masks):
+        """mask-head output [B*max_out, n_cls, M, M] (probabilities)"""
+        self.masks = masks
+        self.graph = None
+
     def _launch(self):
-        L, B, st, ck = hip.lib(), self.B, hip.stream_ptr(self.dev), hip.check
-        T, D = self.top_n, self.max_out
+        st = hip.stream_ptr(self.dev)
+        self.launch_proposals(st)
+        self.launch_detections(st)
+        if self.with_masks and self.masks is not None:
+            self.launch_masks(st)
+
+    def launch_proposals(self, st=None):
+        """RPN outputs (or bound precomputed proposals) -> rois5 + visiting order -> box-head features (self.box_feats)."""
+        L, B, ck = hip.lib(), self.B, hip.check
+        st = st or hip.stream_ptr(self.dev)
+        T = self.top_n
+        if self.prop_in is not None:
+            _launch_prepare(self, 4, 4, st)
+            self._roi_align_box(st)
+            return
         ck(L.dtc_rpn_topk_decode_sized(self.rpn_lv, 1, B, float(self.im_h), float(self.im_w), hip._ptr(self.rpn_im_hw), 0.0,
                                        self.rpn_ws.data_ptr(), self.rpn_ws.numel(), self.pre_boxes.data_ptr(),
                                        self.pre_scores.data_ptr(), self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
@@ -365,13 +493,33 @@ class C4RegionPath:
                                         self.level_counts.data_ptr(), self.idx_restore.data_ptr(),
                                         self.roi_order.data_ptr(), self.roi_desc.data_ptr(), 1, st), "collect")
         self._roi_align_box(st)
-        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(), 0,
-                                           self.bbox_pred.data_ptr(), None, self.sf.data_ptr(), self.im_size.data_ptr(), B, T,
-                                           self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det, self.det_opt,
-                                           self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
+
+    def launch_detections(self, st=None):
+        """cls_score (probabilities, or logits with cls_logits=True) + bbox_pred -> dets (+ the mask branch's 14x14 features on res4
+        with with_masks: the detection launch maps the scaled boxes, k_min == k_max)."""
+        L, B, ck = hip.lib(), self.B, hip.check
+        st = st or hip.stream_ptr(self.dev)
+        T, D = self.top_n, self.max_out
+        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
+                                           1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
+                                           self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
+                                           self.det_opt, self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
                                            self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D,
-                                           None, st),
+                                           self.m_map if self.with_masks else None, st),
            "postprocess_detections_ex")
+        if self.with_masks:
+            self._roi_align_mask(st)
+
+    def launch_masks(self, st=None):
+        """mask-head outputs [B*D, n_cls, M, M] -> binarised crops (+ COCO RLE strings with with_rle=True)."""
+        FpnRegionPath.launch_masks(self, st)
+
+    def _roi_align_mask(self, st=None):
+        st = st or hip.stream_ptr(self.dev)
+        hip.check(hip.lib().dtc_roi_align_forward_packed_ws(self.feat_lv, 1, self.C, self.feat_code, self.m_desc.data_ptr(),
+                                                            self.B * self.max_out, self.mask_p, self.mask_p, self.sr,
+                                                            self.mask_feats.data_ptr(), self.out_code, self.m_ra_ws.data_ptr(),
+                                                            self.m_ra_ws.numel(), st), "roi_align(c4 mask)")
 
     def _roi_align_box(self, st=None):
         st = st or hip.stream_ptr(self.dev)
@@ -382,6 +530,7 @@ class C4RegionPath:
                                                      self.ra_ws.numel(), st), "roi_align(c4)")
 
     step = FpnRegionPath.step
+    results = FpnRegionPath.results
 
     def box_roialign_bytes(self):
         return (self.feat.numel() * self.feat.element_size() + self.B * self.top_n * 5 * 4 +

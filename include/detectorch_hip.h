@@ -230,6 +230,37 @@ int dtc_fpn_collect_distribute_kept(const float* sorted_boxes, const float* sort
                                     float* rois_by_level, int32_t* level_counts, int32_t* idx_restore, int32_t* roi_order,
                                     float* roi_desc, dtc_stream_t stream);
 
+/* Precomputed (Fast R-CNN) proposals -> the rois of dtc_fpn_collect_distribute, one call for a batch: the test-time preprocessing of
+ * lib/utils/preprocess_sample.py:35-45 -- scale by im_scale (:36), remove_dup_prop (:63-70), add_multilevel_rois_for_test for FPN
+ * (lib/utils/multilevel_rois.py:19-53) -- on the device.
+ *   boxes float32 [B, in_stride, 4] (16-byte aligned) in original-image coordinates; counts int32 [B] (device): rows >= counts[b]
+ *   may hold any bits, NaN included, and are never used; im_scale float32 [B] (the reference's Python-float scale rounded to float32:
+ *   numpy multiplies a float32 array by a Python float in float32); dedup_scale 0.0625 (remove_dup_proposals=True, spatial scale
+ *   1/16) or 0 (no deduplication); k_min..k_max the FPN levels (2, 5), k_min == k_max for one level (C4: every row level 0);
+ *   max_out >= in_stride rows per image in every output, so nothing overflows.
+ * Semantics, per image (bit for bit inside the domain below):
+ *   p = boxes * im_scale (one float32 multiply per coordinate); r = rint(p * dedup_scale) in float32 (np.round: half to even);
+ *   hash = r.(1e3, 1e6, 1e9, 1e12) (exact as an integer); output rows = the unique hashes in ASCENDING order, each the scaled box p
+ *   of its FIRST occurrence (np.unique(hash, return_index=True): :67-68, -0. kept).  dedup_scale 0: every row, in input order.
+ *   Then exactly what dtc_fpn_collect_distribute(rows, in_scores = NULL, ...) writes for them: rois5, roi_levels, n_out,
+ *   rois_by_level + level_counts (the reference's per-level blobs, concatenated), idx_restore (rois_idx_restore_int32), roi_order and
+ *   roi_desc (the visiting order for dtc_roi_align_forward_packed[_ws]), with its rules for rows past n_out.
+ *   src_index int32 [B, max_out] (nullable): np.unique's `index` of each output row (the input row it came from).
+ * Domain: finite |p * dedup_scale| < 8192 (|p| < 131 072 px at 1/16), where the reference's float64 dot product is exact.  Finite rows
+ * outside it have r clamped to +-8192 (deterministic, may merge rows the reference keeps apart); a row with a non-finite scaled
+ * coordinate is dropped (it is neither hashed nor emitted; n_out counts the rows that remain).
+ * Rewritten on every call: n_out, level_counts, roi_levels / roi_order / roi_desc on all max_out rows (as dtc_fpn_collect_distribute);
+ * rows >= n_out[b] of rois5, rois_by_level, idx_restore and src_index are unspecified.
+ * in_stride <= 2048 (DTC_EUNSUPPORTED beyond).  Two launches on `stream` (the deduplication, then dtc_fpn_collect_distribute), no
+ * memset: graph-capturable, and a replay picks up boxes / counts / im_scale rewritten in place.  The workspace
+ * (dtc_prepare_proposals_workspace_bytes, 16-byte aligned) holds the unique rows between the two launches: exclusive to one
+ * in-flight call, no clearing needed. */
+size_t dtc_prepare_proposals_workspace_bytes(int batch, int max_out);
+int dtc_prepare_proposals(const float* boxes, const int32_t* counts, const float* im_scale, int batch, int in_stride,
+                          float dedup_scale, int k_min, int k_max, int max_out, void* workspace, size_t workspace_bytes,
+                          float* rois5, int32_t* roi_levels, int32_t* n_out, float* rois_by_level, int32_t* level_counts,
+                          int32_t* idx_restore, int32_t* roi_order, float* roi_desc, int32_t* src_index, dtc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * A8  Detection post-processing
  * --------------------------------------------------------------------------------------------------------------- */
