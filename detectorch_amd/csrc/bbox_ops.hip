@@ -58,6 +58,32 @@ __global__ __launch_bounds__(64) void box_voting_kernel(const float* __restrict_
   if (lane == 5 && n_voters) n_voters[k] = m;
 }
 
+// one wave per top det, scoring_method other than 'ID': the box as box_voting_kernel (box_vote_one), the score by vote_score over
+// the same voters
+__global__ __launch_bounds__(64) void box_voting_scored_kernel(const float* __restrict__ top, int t, const float* __restrict__ all,
+                                                               int a, float thresh, int method, float beta, float* __restrict__ out,
+                                                               int32_t* __restrict__ n_voters) {
+  __shared__ int vl[kVoteMax];
+  __shared__ VoteScratch vs;
+  const int k = blockIdx.x, lane = threadIdx.x;
+  const float* tp = top + (size_t)k * 5;
+  const float4 B = make_float4(tp[0], tp[1], tp[2], tp[3]);
+  auto box = [&](int j) { const float* ap = all + (size_t)j * 5; return make_float4(ap[0], ap[1], ap[2], ap[3]); };
+  auto score = [&](int j) { return all[(size_t)j * 5 + 4]; };
+  int m = 0;
+  const float v = box_vote_one(
+      B, lane < 4 ? tp[lane] : 0.f, a, thresh, [](int) { return true; }, box, [&](int j, int c) { return all[(size_t)j * 5 + c]; },
+      score, vl, lane, &m);
+  float sc = tp[4];                                                                   // no voter: the score stays
+  if (m > 0) {
+    vote_words(B, a, thresh, [](int) { return true; }, box, vs, lane);
+    sc = vote_score(method, beta, vs, (a + 63) >> 6, m, score, [&](int j) { return iou_bbox(B, box(j)); }, lane);
+  }
+  if (lane < 4) out[(size_t)k * 5 + lane] = v;                                         // :295 np.average
+  if (lane == 4) out[(size_t)k * 5 + 4] = sc;                                          // :297-323
+  if (lane == 5 && n_voters) n_voters[k] = m;
+}
+
 }  // namespace dtc
 
 DTC_API int dtc_bbox_overlaps(const float* boxes, int n, int box_cols, const float* query_boxes, int k, int query_cols,
@@ -82,6 +108,23 @@ DTC_API int dtc_box_voting(const float* top_dets, int n_top, const float* all_de
   if (n_all > dtc::kVoteMax) return DTC_EUNSUPPORTED;
   hipLaunchKernelGGL(dtc::box_voting_kernel, dim3(n_top), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), top_dets, n_top,
                      all_dets, n_all, thresh, top_dets_out, n_voters);
+  DTC_CHECK_LAUNCH();
+  return DTC_OK;
+}
+
+DTC_API int dtc_box_voting_scored(const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh,
+                                  const dtc_vote_scoring* scoring, float* top_dets_out, int32_t* n_voters, dtc_stream_t stream) {
+  if (scoring && (scoring->method < dtc::kVoteID || scoring->method > dtc::kVoteQuasiSum || !(scoring->beta > 0.f) ||
+                  !std::isfinite(scoring->beta)))
+    return DTC_EINVAL;
+  if (!scoring || scoring->method == dtc::kVoteID)
+    return dtc_box_voting(top_dets, n_top, all_dets, n_all, thresh, top_dets_out, n_voters, stream);
+  if (n_top < 0 || n_all < 0) return DTC_EINVAL;
+  if (n_top == 0) return DTC_OK;
+  if (!top_dets || !top_dets_out || (n_all > 0 && !all_dets)) return DTC_EINVAL;
+  if (n_all > dtc::kVoteMax) return DTC_EUNSUPPORTED;
+  hipLaunchKernelGGL(dtc::box_voting_scored_kernel, dim3(n_top), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), top_dets, n_top,
+                     all_dets, n_all, thresh, scoring->method, scoring->beta, top_dets_out, n_voters);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }

@@ -361,6 +361,80 @@ __global__ __launch_bounds__(64) void det_soft_nms_kernel(DetParams p, float sig
   if (lane == 0) p.keep_count[seg] = N;
 }
 
+// ---- vote scoring of the kept rows (box_voting(nms_dets, dets_j, thresh, scoring_method), result_utils.py:145-151, scoring other than
+// 'ID'): the scorings rewrite the score column and the limit (:154-163) ranks the VOTED scores, so every kept row of every segment is
+// scored here, BEFORE det_finalize.  One workgroup per (class, image) segment stages the segment's candidates (dets_j: roi ascending
+// from the bitmap, undecayed scores) once in LDS (20 B each: <= 80 KB at R = 4096); its waves take the kept entries in turn (Soft-NMS:
+// selection order, the pre-vote box) and form the voter set as ballot words, then the score (box_vote.h: vote_score, the
+// single-segment drop-in's body).  The voted score replaces the score half of the kept key (det_finalize's limit and the Soft-NMS
+// emit read it) and goes to v_scores[seg, roi] (the hard-NMS emit reads it there instead of q_scores).  The boxes are voted after
+// the limit by det_vote, as with 'ID' (the box vote does not depend on the scores).
+constexpr int kVsThreads = 256;
+struct VoteScoreParams {
+  const int32_t* n_rois;      // [B] or NULL
+  const uint64_t* cand_bits;  // [S, 64]
+  const float* q_boxes;       // [S, R, 4]
+  const float* q_scores;      // [S, R]
+  const int32_t* keep_count;  // [S]
+  uint64_t* kept_key;         // [S, R]
+  float* v_scores;            // [S, R]
+  int R, n_cls, method;
+  float thresh, beta;
+};
+
+__global__ __launch_bounds__(kVsThreads) void det_vote_score_kernel(VoteScoreParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ uint64_t cbits_s[kCandWords];
+  __shared__ int wpre_s[kCandWords];
+  __shared__ VoteScratch vs_s[kVsThreads / 64];
+  const int seg = blockIdx.y * (p.n_cls - 1) + blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nk = p.keep_count[seg];
+  if (nk == 0) return;
+  const int nr = p.n_rois ? min(p.n_rois[blockIdx.y], p.R) : p.R;
+  const int nw = (nr + 63) >> 6;
+  float4* cb = reinterpret_cast<float4*>(smem);                     // [R] candidate boxes, dets_j order
+  float* cs = reinterpret_cast<float*>(cb + p.R);                    // [R] their scores
+  if (wv == 0) {                                                     // the bitmap and the popcount prefix of its words
+    const uint64_t w = lane < nw ? p.cand_bits[(size_t)seg * kCandWords + lane] : 0ull;
+    const int pc = __builtin_popcountll(w);
+    int incl = pc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    cbits_s[lane] = w;
+    wpre_s[lane] = incl - pc;
+  }
+  __syncthreads();
+  const float4* qb = reinterpret_cast<const float4*>(p.q_boxes) + (size_t)seg * p.R;
+  const float* qs = p.q_scores + (size_t)seg * p.R;
+  for (int r = tid; r < nr; r += kVsThreads) {
+    const uint64_t w = cbits_s[r >> 6];
+    if ((w >> (r & 63)) & 1ull) {
+      const int k = wpre_s[r >> 6] + __builtin_popcountll(w & ((1ull << (r & 63)) - 1ull));
+      cb[k] = qb[r];
+      cs[k] = qs[r];
+    }
+  }
+  __syncthreads();
+  const int n = wpre_s[63] + __builtin_popcountll(cbits_s[63]);      // candidates of the segment
+  VoteScratch& vs = vs_s[wv];
+  uint64_t* K = p.kept_key + (size_t)seg * p.R;
+  for (int e = wv; e < nk; e += kVsThreads / 64) {
+    const uint64_t key = K[e];
+    const uint32_t r = desc_key_index(key);
+    const float4 B = qb[r];
+    const int m = vote_words(B, n, p.thresh, [](int) { return true; }, [&](int k) { return cb[k]; }, vs, lane);
+    float sc = desc_key_score(key);                                    // no voter: the score stays
+    if (m > 0)
+      sc = vote_score(p.method, p.beta, vs, (n + 63) >> 6, m, [&](int k) { return cs[k]; },
+                      [&](int k) { return iou_bbox(B, cb[k]); }, lane);
+    if (lane == 0) {
+      K[e] = make_desc_key(sc, r);
+      p.v_scores[(size_t)seg * p.R + r] = sc;
+    }
+  }
+}
+
 constexpr int kFinThreads = 1024;
 constexpr int kFinMaxCls = 256;
 
@@ -368,7 +442,7 @@ struct FinParams {
   const uint64_t* kept_key;   // [S, R] sort keys of the kept boxes (det_candidates' NMS): ~ordered score << 32 | candidate index q
   const int32_t* keep_count;  // [S]
   const float* q_boxes;       // [S, R, 4]
-  const float* q_scores;      // [S, R]
+  const float* q_scores;      // [S, R]  the emitted score of a hard-NMS row (the voted scores with a vote scoring: v_scores)
   const int32_t* q_roi;       // [S, R]
   const float* scale;         // [B]
   int R, n_cls, max_det, max_out;
@@ -705,8 +779,8 @@ static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace dtc
 
 namespace dtc {
-struct DetPlan { size_t sorted_boxes, q_boxes, q_scores, q_roi, cand_count, kept_key, keep_count, sm_stats, cand_bits, total; };
-static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits = false) {
+struct DetPlan { size_t sorted_boxes, q_boxes, q_scores, q_roi, cand_count, kept_key, keep_count, sm_stats, cand_bits, v_scores, total; };
+static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits = false, bool with_vscores = false) {
   DetPlan d;
   const size_t S = (size_t)batch * (n_cls - 1);
   size_t o = 0;
@@ -719,6 +793,7 @@ static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits = false) {
   d.keep_count = o; o += al256(S * sizeof(int32_t));
   d.sm_stats = o; o += al256((size_t)batch * R * 2 * sizeof(double));
   d.cand_bits = o; if (with_bits) o += al256(S * kCandWords * sizeof(uint64_t));
+  d.v_scores = o; if (with_vscores) o += al256(S * R * sizeof(float));
   d.total = o;
   return d;
 }
@@ -742,6 +817,27 @@ static int det_options_check(const dtc_det_options* opt, int* soft, bool* vote) 
   return DTC_OK;
 }
 
+// dtc_vote_scoring validation (host only) -> DTC_OK / DTC_EINVAL; *method = the scoring (kVoteID for NULL)
+static int vote_scoring_check(const dtc_det_options* opt, const dtc_vote_scoring* scoring, int* method) {
+  *method = dtc::kVoteID;
+  if (!scoring) return DTC_OK;
+  if (scoring->method < dtc::kVoteID || scoring->method > dtc::kVoteQuasiSum) return DTC_EINVAL;
+  if (!(scoring->beta > 0.f) || !std::isfinite(scoring->beta)) return DTC_EINVAL;
+  if (scoring->method != dtc::kVoteID && !(opt && opt->bbox_vote == 1)) return DTC_EINVAL;
+  *method = scoring->method;
+  return DTC_OK;
+}
+
+DTC_API size_t dtc_postprocess_detections_ex2_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt,
+                                                              const dtc_vote_scoring* scoring) {
+  int soft, method;
+  bool vote;
+  if (batch < 1 || max_rois < 1 || n_cls < 2 || det_options_check(opt, &soft, &vote) != DTC_OK ||
+      vote_scoring_check(opt, scoring, &method) != DTC_OK)
+    return 0;
+  return dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote, method != dtc::kVoteID).total;
+}
+
 DTC_API size_t dtc_postprocess_detections_ex_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt) {
   int soft;
   bool vote;
@@ -755,10 +851,12 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
                                        float score_thresh, float nms_thresh, int max_det, void* workspace,
                                        size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
                                        int32_t* det_count, int max_out, dtc_stream_t stream, const dtc_fpn_map_out* fpn = nullptr,
-                                       const dtc_det_options* opt = nullptr) {
-  int soft;
+                                       const dtc_det_options* opt = nullptr, const dtc_vote_scoring* scoring = nullptr) {
+  int soft, method;
   bool vote;
   if (det_options_check(opt, &soft, &vote) != DTC_OK) return DTC_EINVAL;
+  if (vote_scoring_check(opt, scoring, &method) != DTC_OK) return DTC_EINVAL;
+  const bool scored = method != dtc::kVoteID;
   if (batch < 0 || max_rois < 1 || n_cls < 2 || n_cls - 1 > dtc::kFinMaxCls || max_out < 1) return DTC_EINVAL;
   if (fpn) {
     if (!det_rois_scaled || !fpn->rois5 || !fpn->roi_levels || !fpn->n_out || !fpn->rois_by_level || !fpn->level_counts || !fpn->idx_restore ||
@@ -771,7 +869,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   if (!cls_score || !workspace || !dets || !det_roi || !det_count) return DTC_EINVAL;
   if (!decoded_boxes && (!rois5 || !bbox_pred || !scaling_factor || !im_size)) return DTC_EINVAL;
   if (decoded_boxes && det_rois_scaled) return DTC_EINVAL;
-  const dtc::DetPlan pl = dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote);
+  const dtc::DetPlan pl = dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote, scored);
   if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -810,8 +908,19 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
                        opt->soft_sigma, nms_thresh, opt->soft_score_thresh, soft);
     DTC_CHECK_LAUNCH();
   }
+  float* v_scores = scored ? reinterpret_cast<float*>(w + pl.v_scores) : nullptr;
+  if (scored) {
+    dtc::VoteScoreParams vp;
+    vp.n_rois = n_rois; vp.cand_bits = p.cand_bits; vp.q_boxes = p.q_boxes; vp.q_scores = p.q_scores; vp.keep_count = keep_count;
+    vp.kept_key = kept_key; vp.v_scores = v_scores; vp.R = max_rois; vp.n_cls = n_cls; vp.method = method;
+    vp.thresh = opt->bbox_vote_thresh; vp.beta = scoring->beta;
+    const size_t vsm = (size_t)max_rois * (sizeof(float4) + sizeof(float));
+    if (vsm > 48 * 1024) { DTC_RAISE_LDS_ONCE(dtc::det_vote_score_kernel, 4096 * (sizeof(float4) + sizeof(float))); }
+    hipLaunchKernelGGL(dtc::det_vote_score_kernel, dim3(n_cls - 1, batch), dim3(dtc::kVsThreads), vsm, s, vp);
+    DTC_CHECK_LAUNCH();
+  }
   dtc::FinParams f;
-  f.kept_key = kept_key; f.keep_count = keep_count; f.q_boxes = p.q_boxes; f.q_scores = p.q_scores;
+  f.kept_key = kept_key; f.keep_count = keep_count; f.q_boxes = p.q_boxes; f.q_scores = scored ? v_scores : p.q_scores;
   f.q_roi = p.q_roi; f.scale = scaling_factor; f.R = max_rois; f.n_cls = n_cls; f.max_det = max_det; f.max_out = max_out;
   f.dets = dets; f.det_roi = det_roi; f.det_rois_scaled = det_rois_scaled; f.det_count = det_count;
   f.fm.on = fpn && !vote ? 1 : 0;            // with voting the mapping follows the vote (det_fpn_map)
@@ -901,4 +1010,17 @@ DTC_API int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_r
   return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, decoded_boxes, scaling_factor,
                                      im_size, batch, max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace,
                                      workspace_bytes, dets, det_roi, det_rois_scaled, det_count, max_out, stream, fpn, opt);
+}
+
+DTC_API int dtc_postprocess_detections_ex2(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
+                                           const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor,
+                                           const float* im_size, int batch, int max_rois, int n_cls, float wx, float wy, float ww,
+                                           float wh, float score_thresh, float nms_thresh, int max_det, const dtc_det_options* opt,
+                                           const dtc_vote_scoring* scoring, void* workspace, size_t workspace_bytes, float* dets,
+                                           int32_t* det_roi, float* det_rois_scaled, int32_t* det_count, int max_out,
+                                           const dtc_fpn_map_out* fpn, dtc_stream_t stream) {
+  if (decoded_boxes && fpn) return DTC_EINVAL;
+  return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, decoded_boxes, scaling_factor,
+                                     im_size, batch, max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace,
+                                     workspace_bytes, dets, det_roi, det_rois_scaled, det_count, max_out, stream, fpn, opt, scoring);
 }

@@ -65,6 +65,32 @@ def det_options(do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear',
                       1 if do_bbox_vote else 0, float(bbox_vote_thresh))
 
 
+class VoteScoring(C.Structure):
+    """struct dtc_vote_scoring (include/detectorch_hip.h)"""
+    _fields_ = [("method", C.c_int32), ("beta", C.c_float)]
+
+
+# box_voting's scoring_method (lib/utils/boxes.py:280-329) -> DTC_VOTE_*
+VOTE_METHODS = {"ID": 0, "TEMP_AVG": 1, "AVG": 2, "IOU_AVG": 3, "GENERALIZED_AVG": 4, "QUASI_SUM": 5}
+
+
+def vote_scoring(method='ID', beta=1.0):
+    """box_voting's scoring_method / beta as a dtc_vote_scoring, or None for 'ID' (the score is left as it is)."""
+    if method not in VOTE_METHODS:
+        raise NotImplementedError('Unknown scoring method {}'.format(method))               # boxes.py:324-327
+    if method == 'ID':
+        return None
+    return VoteScoring(VOTE_METHODS[method], float(beta))
+
+
+def det_options_scoring(options=None):
+    """A region path's det_options dict (det_options' keywords + bbox_vote_method) -> (DetOptions or None, VoteScoring or
+    None).  bbox_vote_method counts only with do_bbox_vote, as in box_results_with_nms_and_limit; an unknown one raises."""
+    d = dict(options or {})
+    scoring = vote_scoring(d.pop('bbox_vote_method', 'ID'))
+    return det_options(**d), (scoring if d.get('do_bbox_vote') else None)
+
+
 _lib = None
 
 
@@ -141,6 +167,11 @@ def lib():
     L.dtc_postprocess_detections_ex.argtypes = [p, p, p, i, p, p, p, p, i, i, i, f, f, f, f, f, f, i, C.POINTER(DetOptions), p,
                                                 sz, p, p, p, p, i, C.POINTER(FpnMapOut), p]
     L.dtc_postprocess_detections_ex.restype = i
+    L.dtc_postprocess_detections_ex2_workspace_bytes.argtypes = [i, i, i, C.POINTER(DetOptions), C.POINTER(VoteScoring)]
+    L.dtc_postprocess_detections_ex2_workspace_bytes.restype = sz
+    L.dtc_postprocess_detections_ex2.argtypes = [p, p, p, i, p, p, p, p, i, i, i, f, f, f, f, f, f, i, C.POINTER(DetOptions),
+                                                 C.POINTER(VoteScoring), p, sz, p, p, p, p, i, C.POINTER(FpnMapOut), p]
+    L.dtc_postprocess_detections_ex2.restype = i
     L.dtc_bias_act.argtypes = [p, p, p, i, i, i, i, i, i, i, i, p]
     L.dtc_bias_act.restype = i
     L.dtc_mask_paste.argtypes = [p, p, i, i, p, p, p, i, i, f, i, p, ll, p, p, p, p, p]
@@ -155,6 +186,8 @@ def lib():
     L.dtc_bbox_overlaps.restype = i
     L.dtc_box_voting.argtypes = [p, i, p, i, f, p, p, p]
     L.dtc_box_voting.restype = i
+    L.dtc_box_voting_scored.argtypes = [p, i, p, i, f, C.POINTER(VoteScoring), p, p, p]
+    L.dtc_box_voting_scored.restype = i
     L.dtc_soft_nms.argtypes = [p, i, f, f, f, i, p, p, p, p]
     L.dtc_soft_nms.restype = i
     L.dtc_bbox_transform.argtypes = [p, p, i, i, f, f, f, f, i, f, f, p, p]
@@ -475,9 +508,12 @@ def prepare_proposals(boxes, counts, im_scale, dedup_scale=0.0625, k_min=2, k_ma
     return out
 
 
-def det_workspace_bytes(batch, max_rois, n_cls, opt=None):
-    """dtc_postprocess_detections_ex_workspace_bytes (opt: a DetOptions or None)"""
-    need = lib().dtc_postprocess_detections_ex_workspace_bytes(int(batch), int(max_rois), int(n_cls), opt)
+def det_workspace_bytes(batch, max_rois, n_cls, opt=None, bbox_vote_method='ID', scoring=None):
+    """dtc_postprocess_detections_ex2_workspace_bytes (opt: a DetOptions or None; the vote scoring as a method name or, when
+    given, a VoteScoring)"""
+    if scoring is None:
+        scoring = vote_scoring(bbox_vote_method)
+    need = lib().dtc_postprocess_detections_ex2_workspace_bytes(int(batch), int(max_rois), int(n_cls), opt, scoring)
     if need == 0:
         raise ValueError("invalid detection post-processing shape or options")
     return need
@@ -486,11 +522,12 @@ def det_workspace_bytes(batch, max_rois, n_cls, opt=None):
 def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size, weights=(10., 10., 5., 5.),
                            score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None, scores_are_logits=False,
                            do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False,
-                           bbox_vote_thresh=0.8):
-    """dtc_postprocess_detections_ex.  rois5 [B,R,5], cls_score [B,R,C], bbox_pred [B,R,4C], scaling_factor [B], im_size [B,2].
+                           bbox_vote_thresh=0.8, bbox_vote_method='ID'):
+    """dtc_postprocess_detections_ex2.  rois5 [B,R,5], cls_score [B,R,C], bbox_pred [B,R,4C], scaling_factor [B], im_size [B,2].
     scores_are_logits=True: cls_score holds the raw cls_score-layer output and the softmax of detector.py:281 is folded into
     the kernel; the probability map is never materialised.  do_soft_nms / soft_nms_sigma / soft_nms_method / do_bbox_vote /
-    bbox_vote_thresh: the reference's options of box_results_with_nms_and_limit (result_utils.py:96-168; 'ID' vote scoring).
+    bbox_vote_thresh / bbox_vote_method: the reference's options of box_results_with_nms_and_limit (result_utils.py:96-168;
+    bbox_vote_method is box_voting's scoring_method, beta 1.0 as there).
     -> (dets [B,max_out,6], det_roi [B,max_out], det_rois_scaled [B,max_out,4], det_count [B])"""
     dev = _require_cuda(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size)
     B, R, ncls = cls_score.shape
@@ -498,7 +535,8 @@ def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, 
         max_out = 128 if max_det > 0 else R * (ncls - 1)
     L_ = lib()
     opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
-    need = det_workspace_bytes(B, R, ncls, opt)
+    scoring = vote_scoring(bbox_vote_method)
+    need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
     if ws is None or ws.numel() < need:
         ws = workspace(need, dev)
     f32, i32 = torch.float32, torch.int32
@@ -509,18 +547,19 @@ def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, 
     rois5, cls_score, bbox_pred = rois5.contiguous(), cls_score.contiguous(), bbox_pred.contiguous()
     scaling_factor, im_size = scaling_factor.to(f32).contiguous(), im_size.to(f32).contiguous()
     with torch.cuda.device(dev):
-        rc = L_.dtc_postprocess_detections_ex(rois5.data_ptr(), _ptr(n_rois), cls_score.data_ptr(), 1 if scores_are_logits else 0,
-                                              bbox_pred.data_ptr(), None, scaling_factor.data_ptr(), im_size.data_ptr(), B, R, ncls,
-                                              *[float(w) for w in weights], float(score_thresh), float(nms_thresh), int(max_det),
-                                              opt, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(),
-                                              det_scaled.data_ptr(), det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections_ex")
+        rc = L_.dtc_postprocess_detections_ex2(rois5.data_ptr(), _ptr(n_rois), cls_score.data_ptr(), 1 if scores_are_logits else 0,
+                                               bbox_pred.data_ptr(), None, scaling_factor.data_ptr(), im_size.data_ptr(), B, R, ncls,
+                                               *[float(w) for w in weights], float(score_thresh), float(nms_thresh), int(max_det),
+                                               opt, scoring, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(),
+                                               det_scaled.data_ptr(), det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
+    check(rc, "dtc_postprocess_detections_ex2")
     return dets, det_roi, det_scaled, det_count
 
 
 def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None,
-                          do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8):
-    """box_results_with_nms_and_limit on decoded boxes (dtc_postprocess_detections_ex with decoded_boxes): scores [B,R,C],
+                          do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8,
+                          bbox_vote_method='ID'):
+    """box_results_with_nms_and_limit on decoded boxes (dtc_postprocess_detections_ex2 with decoded_boxes): scores [B,R,C],
     decoded boxes [B,R,4C] -> (dets [B,max_out,6], det_roi [B,max_out], det_count [B]).  Options as postprocess_detections."""
     dev = _require_cuda(scores, boxes, n_rois)
     B, R, ncls = scores.shape
@@ -528,7 +567,8 @@ def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thr
         max_out = 128 if max_det > 0 else R * (ncls - 1)
     L_ = lib()
     opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
-    need = det_workspace_bytes(B, R, ncls, opt)
+    scoring = vote_scoring(bbox_vote_method)
+    need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
     if ws is None or ws.numel() < need:
         ws = workspace(need, dev)
     dets = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
@@ -536,11 +576,11 @@ def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thr
     det_count = torch.empty((B,), dtype=torch.int32, device=dev)
     scores, boxes = scores.contiguous(), boxes.contiguous()
     with torch.cuda.device(dev):
-        rc = L_.dtc_postprocess_detections_ex(None, _ptr(n_rois), scores.data_ptr(), 0, None, boxes.data_ptr(), None, None, B, R,
-                                              ncls, 1., 1., 1., 1., float(score_thresh), float(nms_thresh), int(max_det), opt,
-                                              ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(), None,
-                                              det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections_ex")
+        rc = L_.dtc_postprocess_detections_ex2(None, _ptr(n_rois), scores.data_ptr(), 0, None, boxes.data_ptr(), None, None, B, R,
+                                               ncls, 1., 1., 1., 1., float(score_thresh), float(nms_thresh), int(max_det), opt,
+                                               scoring, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(), None,
+                                               det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
+    check(rc, "dtc_postprocess_detections_ex2")
     return dets, det_roi, det_count
 
 
@@ -597,17 +637,19 @@ def bbox_overlaps(boxes, query_boxes):
     return out
 
 
-def box_voting(top_dets, all_dets, thresh):
-    """dtc_box_voting ('ID' scoring): [T,5], [A,5] float32 CUDA -> ([T,5], n_voters int32 [T])."""
+def box_voting(top_dets, all_dets, thresh, scoring_method='ID', beta=1.0):
+    """dtc_box_voting_scored: [T,5], [A,5] float32 CUDA -> ([T,5], n_voters int32 [T]); scoring_method / beta as box_voting's
+    (lib/utils/boxes.py:280-329; 'ID' leaves column 4, the others write the voted score)."""
+    scoring = vote_scoring(scoring_method, beta)
     dev = _require_cuda(top_dets, all_dets)
     top_dets, all_dets = top_dets.contiguous(), all_dets.contiguous()
     t, a = top_dets.shape[0], all_dets.shape[0]
     out = torch.empty((t, 5), dtype=torch.float32, device=dev)
     nv = torch.zeros((max(t, 1),), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_box_voting(top_dets.data_ptr(), t, all_dets.data_ptr(), a, float(thresh), out.data_ptr(),
-                                  nv.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_box_voting")
+        rc = lib().dtc_box_voting_scored(top_dets.data_ptr(), t, all_dets.data_ptr(), a, float(thresh), scoring, out.data_ptr(),
+                                         nv.data_ptr(), stream_ptr(dev))
+    check(rc, "dtc_box_voting_scored")
     return out, nv[:t]
 
 

@@ -586,7 +586,8 @@ class detector(nn.Module):
 
     @torch.no_grad()
     def forward_batched(self, images, scaling_factor, im_size, blob_hw=None, do_soft_nms=False, soft_nms_sigma=0.5,
-                        soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8, proposals=None, proposal_counts=None):
+                        soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8, proposals=None, proposal_counts=None,
+                        bbox_vote_method='ID'):
         """Mask / Faster R-CNN FPN forward for a BATCH (lib/model/detector.py:233-286 + :99-112 + eval_mask_FPN.ipynb:231-262,
         which the reference runs image by image with 21 synchronising copies each).
           images [B,3,H,W] prepared blobs of one padded size (utils.blob.im_list_to_blob); scaling_factor [B]; im_size [B,2]
@@ -594,8 +595,9 @@ class detector(nn.Module):
           resized size rounded up to the stride 32 (hip.prep_images' sizes); the RPN of image b then clips, filters and ranks
           exactly as a batch-1 run on that blob would (dtc_rpn_topk_decode_sized; RoIAlign still reads the padded maps).  None:
           every image is the whole blob.
-          do_soft_nms / soft_nms_sigma / soft_nms_method / do_bbox_vote / bbox_vote_thresh: the reference's test-time options of
-          box_results_with_nms_and_limit (result_utils.py:96-168, 'ID' vote scoring), run inside launch_detections.
+          do_soft_nms / soft_nms_sigma / soft_nms_method / do_bbox_vote / bbox_vote_thresh / bbox_vote_method: the reference's
+          test-time options of box_results_with_nms_and_limit (result_utils.py:96-168; bbox_vote_method is box_voting's
+          scoring_method, beta 1.0 as there), run inside launch_detections.
         Everything stays on the device:  backbone(B) -> RPN heads -> FpnRegionPath.launch_proposals (top-k, NMS, collect,
         distribute, RoIAlign 7x7 in visiting order) -> fc6/fc7/cls/bbox -> launch_detections (softmax folded in, class decode,
         80-class NMS, top-100, mask-branch RoIAlign 14x14) -> mask head convs -> launch_masks (paste, binarise, COCO RLE).
@@ -612,10 +614,14 @@ class detector(nn.Module):
             raise ValueError("this model has an RPN head: its proposals come from it (proposals= is for models without one)")
         if not self.use_rpn_head and proposals is None:
             raise ValueError("a model without an RPN head needs precomputed proposals (proposals=)")
+        if bbox_vote_method not in hip.VOTE_METHODS:
+            raise NotImplementedError('Unknown scoring method {}'.format(bbox_vote_method))      # boxes.py:324-327
         det_options = None
         if do_soft_nms or do_bbox_vote:
             det_options = dict(do_soft_nms=bool(do_soft_nms), soft_nms_sigma=float(soft_nms_sigma), soft_nms_method=soft_nms_method,
                                do_bbox_vote=bool(do_bbox_vote), bbox_vote_thresh=float(bbox_vote_thresh))
+            if do_bbox_vote and bbox_vote_method != 'ID':
+                det_options['bbox_vote_method'] = bbox_vote_method
         B, h, w = images.size(0), images.size(2), images.size(3)
         dev = images.device
         sf = torch.as_tensor(scaling_factor, dtype=torch.float32, device=dev).reshape(B).contiguous()

@@ -74,9 +74,10 @@ class FpnRegionPath:
                  feat_dtype=torch.float32, crop_capacity=8 << 20, cls_logits=False, with_rle=False,
                  rle_runs_stride=4096, rle_str_stride=8192, det_options=None):
         """det_options: dict of the reference's test-time options of box_results_with_nms_and_limit (do_soft_nms, soft_nms_sigma,
-        soft_nms_method, do_bbox_vote, bbox_vote_thresh; hip.det_options), baked into the detection launch; None: hard NMS."""
+        soft_nms_method, do_bbox_vote, bbox_vote_thresh, bbox_vote_method; hip.det_options_scoring), baked into the detection
+        launch; None: hard NMS."""
         self.B, self.dev = batch, device
-        self.det_opt = hip.det_options(**(det_options or {}))
+        self.det_opt, self.det_scoring = hip.det_options_scoring(det_options)
         self.with_rle, self.rle_runs_stride, self.rle_str_stride = with_rle, int(rle_runs_stride), int(rle_str_stride)
         self.cls_logits = cls_logits       # bind() receives the cls_score layer's raw output; softmax folded into the kernel
         self.C, self.n_cls = channels, n_cls
@@ -118,7 +119,7 @@ class FpnRegionPath:
         D = self.max_out
         self.dets, self.det_roi = torch.zeros((B, D, 6), device=dev), torch.zeros((B, D), dtype=i32, device=dev)
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
-        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, self.n_cls, self.det_opt), dev)
+        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, self.n_cls, self.det_opt, scoring=self.det_scoring), dev)
         self.det_count_c = e(B, 1, dtype=i32)
         self.m_rois5, self.m_levels, self.m_n = e(B, D, 5), e(B, D, dtype=i32), e(B, dtype=i32)
         self.m_by_level, self.m_level_counts, self.m_restore = e(B, D, 4), e(B, 4, dtype=i32), e(B, D, dtype=i32)
@@ -242,14 +243,15 @@ class FpnRegionPath:
         L, B, ck = hip.lib(), self.B, hip.check
         st = st or hip.stream_ptr(self.dev)
         T, D = self.top_n, self.max_out
-        # one entry for both forms (dtc_postprocess_detections_ex): with the fused mask-branch mapping (fpn != NULL), or without
-        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
-                                           1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
-                                           self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
-                                           self.det_opt, self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
-                                           self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D,
-                                           self.m_map if self.fused_mask_map else None, st),
-           "postprocess_detections_ex")
+        # one entry for both forms (dtc_postprocess_detections_ex2): with the fused mask-branch mapping (fpn != NULL), or without
+        ck(L.dtc_postprocess_detections_ex2(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
+                                            1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
+                                            self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
+                                            self.det_opt, self.det_scoring, self.det_ws.data_ptr(), self.det_ws.numel(),
+                                            self.dets.data_ptr(), self.det_roi.data_ptr(), self.det_scaled.data_ptr(),
+                                            self.det_count.data_ptr(), D,
+                                            self.m_map if self.fused_mask_map else None, st),
+           "postprocess_detections_ex2")
         if self.fused_mask_map:
             self._roi_align_mask(st)
             return
@@ -374,7 +376,7 @@ class C4RegionPath:
         self.crop_capacity = crop_capacity
         self.mask_p = 14
         self.prop_in = None
-        self.det_opt = hip.det_options(**(det_options or {}))
+        self.det_opt, self.det_scoring = hip.det_options_scoring(det_options)
         self.pre, self.post, self.top_n = pre_nms_top_n, post_nms_top_n, post_nms_top_n
         self.thresh, self.pooled, self.sr = rpn_nms_thresh, pooled, sampling_ratio
         self.max_det, self.max_out, self.im_h, self.im_w = max_det, max_out, im_h, im_w
@@ -402,7 +404,7 @@ class C4RegionPath:
         D = max_out
         self.dets, self.det_roi = torch.zeros((B, D, 6), device=dev), torch.zeros((B, D), dtype=i32, device=dev)
         self.det_scaled, self.det_count = torch.zeros((B, D, 4), device=dev), e(B, dtype=i32)
-        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, n_cls, self.det_opt), dev)
+        self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, n_cls, self.det_opt, scoring=self.det_scoring), dev)
         if with_masks:
             if D > 512:
                 raise ValueError("with_masks needs max_out <= 512 (the detection launch's fused level mapping)")
@@ -500,13 +502,14 @@ class C4RegionPath:
         L, B, ck = hip.lib(), self.B, hip.check
         st = st or hip.stream_ptr(self.dev)
         T, D = self.top_n, self.max_out
-        ck(L.dtc_postprocess_detections_ex(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
-                                           1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
-                                           self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
-                                           self.det_opt, self.det_ws.data_ptr(), self.det_ws.numel(), self.dets.data_ptr(),
-                                           self.det_roi.data_ptr(), self.det_scaled.data_ptr(), self.det_count.data_ptr(), D,
-                                           self.m_map if self.with_masks else None, st),
-           "postprocess_detections_ex")
+        ck(L.dtc_postprocess_detections_ex2(self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(),
+                                            1 if self.cls_logits else 0, self.bbox_pred.data_ptr(), None, self.sf.data_ptr(),
+                                            self.im_size.data_ptr(), B, T, self.n_cls, 10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det,
+                                            self.det_opt, self.det_scoring, self.det_ws.data_ptr(), self.det_ws.numel(),
+                                            self.dets.data_ptr(), self.det_roi.data_ptr(), self.det_scaled.data_ptr(),
+                                            self.det_count.data_ptr(), D,
+                                            self.m_map if self.with_masks else None, st),
+           "postprocess_detections_ex2")
         if self.with_masks:
             self._roi_align_mask(st)
 

@@ -111,42 +111,19 @@ def bbox_overlaps(boxes, query_boxes):
 
 def box_voting(top_dets, all_dets, thresh, scoring_method='ID', beta=1.0):
     """Bounding-box voting (boxes.py:280-329): every row of top_dets [N,5] gets its box replaced by the score-weighted
-    mean of the all_dets [M,5] that overlap it by IoU >= thresh (device: dtc_box_voting).  scoring_method other than 'ID'
-    also rewrites the score column from the voters' scores -- small host statistics over the device IoU matrix."""
-    methods = ('ID', 'TEMP_AVG', 'AVG', 'IOU_AVG', 'GENERALIZED_AVG', 'QUASI_SUM')
-    if scoring_method not in methods:
-        raise NotImplementedError('Unknown scoring method {}'.format(scoring_method))       # boxes.py:324-327
+    mean of the all_dets [M,5] that overlap it by IoU >= thresh; scoring_method other than 'ID' also rewrites the score
+    column from the voters' scores.  One device call for every method (dtc_box_voting_scored, M <= 8192)."""
+    hip.vote_scoring(scoring_method, beta)            # NotImplementedError for an unknown method (boxes.py:324-327)
     top = np.ascontiguousarray(top_dets, dtype=np.float32)
     alld = np.ascontiguousarray(all_dets, dtype=np.float32)
     if top.shape[0] == 0:
         return top.copy()
     dev = _dev()
     t_top, t_all = torch.from_numpy(top).to(dev), torch.from_numpy(alld).to(dev)
-    voted, n_voters = hip.box_voting(t_top, t_all, np.float32(thresh))
+    voted, n_voters = hip.box_voting(t_top, t_all, np.float32(thresh), scoring_method, beta)
     if int(n_voters.min().item()) == 0:
         raise ZeroDivisionError("Weights sum to zero, can't be normalized")                 # what np.average raises at :295
-    out = voted.cpu().numpy()
-    if scoring_method == 'ID':
-        return out
-    iou = hip.bbox_overlaps(t_top[:, :4].contiguous(), t_all[:, :4].contiguous()).cpu().numpy()
-    scores_all = alld[:, 4]
-    for k in range(out.shape[0]):
-        sel = np.where(iou[k] >= thresh)[0]
-        ws = scores_all[sel]
-        if scoring_method == 'AVG':                                                          # :311-313
-            out[k, 4] = ws.mean()
-        elif scoring_method == 'IOU_AVG':                                                    # :314-318
-            out[k, 4] = np.average(ws, weights=iou[k, sel])
-        elif scoring_method == 'GENERALIZED_AVG':                                            # :319-321
-            out[k, 4] = np.mean(ws ** beta) ** (1.0 / beta)
-        elif scoring_method == 'QUASI_SUM':                                                  # :322-323
-            out[k, 4] = ws.sum() / float(len(ws)) ** beta
-        else:                                                                                # 'TEMP_AVG' :300-310
-            two = np.vstack((ws, 1.0 - ws))
-            logit = np.log(two / np.max(two, axis=0))
-            soft = np.exp(logit / beta)
-            out[k, 4] = (soft / np.sum(soft, axis=0))[0].mean()
-    return out
+    return voted.cpu().numpy()
 
 
 def xyxy_to_xywh(xyxy):

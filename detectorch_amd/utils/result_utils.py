@@ -88,12 +88,15 @@ def box_results_with_nms_and_limit(scores, boxes, num_classes=81, score_thresh=0
                                    do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False,
                                    bbox_vote_thresh=0.8, bbox_vote_method='ID', max_detections_per_img=100):
     """result_utils.py:96-168 on already decoded+clipped boxes [R,4*num_classes] (numpy in / numpy out).
-    ONE pass on the device -- threshold, 80-class segmented hard NMS or Soft-NMS, optional 'ID' bbox voting, the top-100 limit,
-    one copy back (dtc_postprocess_detections_ex); the reference runs 80 Python iterations, each a host NMS call.  The
-    reference's per-class loop (on the single-segment kernels) remains for the non-'ID' vote scorings and R > 4096."""
+    ONE pass on the device -- threshold, 80-class segmented hard NMS or Soft-NMS, optional bbox voting with any of box_voting's
+    scorings (voted scores before the limit), the top-100 limit, one copy back (dtc_postprocess_detections_ex2); the reference
+    runs 80 Python iterations, each a host NMS call.  The reference's per-class loop (on the single-segment kernels) remains
+    for R > 4096."""
     scores = np.ascontiguousarray(scores, np.float32)
     boxes = np.ascontiguousarray(boxes, np.float32)
-    on_device = (not do_bbox_vote or bbox_vote_method == 'ID') and (not do_soft_nms or soft_nms_method in hip.SOFT_NMS_METHODS)
+    if do_bbox_vote:
+        hip.vote_scoring(bbox_vote_method)             # NotImplementedError for an unknown method, as box_voting raises it
+    on_device = not do_soft_nms or soft_nms_method in hip.SOFT_NMS_METHODS
     if on_device and scores.shape[0] <= 4096 and scores.shape[0] > 0 and num_classes > 1:
         dev = _dev()
         R = scores.shape[0]
@@ -101,7 +104,8 @@ def box_results_with_nms_and_limit(scores, boxes, num_classes=81, score_thresh=0
         bx = torch.from_numpy(boxes[:, :4 * num_classes]).to(dev).reshape(1, R, 4 * num_classes)
         max_out = 256 if max_detections_per_img > 0 else R * (num_classes - 1)
         kw = dict(do_soft_nms=do_soft_nms, soft_nms_sigma=soft_nms_sigma, soft_nms_method=soft_nms_method,
-                  do_bbox_vote=do_bbox_vote, bbox_vote_thresh=bbox_vote_thresh)
+                  do_bbox_vote=do_bbox_vote, bbox_vote_thresh=bbox_vote_thresh,
+                  bbox_vote_method=bbox_vote_method if do_bbox_vote else 'ID')
         dets, _, cnt = hip.box_results_nms_limit(sc, bx, None, score_thresh, overlap_thresh, max_detections_per_img, max_out, **kw)
         n = int(cnt[0].item())
         if n > dets.shape[1]:            # more than max_out rows tie at the limit score (:161 keeps them all)

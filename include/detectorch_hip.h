@@ -371,6 +371,45 @@ int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_rois, con
                                   float* det_rois_scaled, int32_t* det_count, int max_out, const dtc_fpn_map_out* fpn,
                                   dtc_stream_t stream);
 
+/* Scoring of the bbox vote (box_voting's scoring_method and beta, lib/utils/boxes.py:280-329; Detectron's
+ * TEST.BBOX_VOTE.SCORING_METHOD / SCORING_METHOD_BETA).  'ID' keeps the score; every other method rewrites it from the scores of
+ * the voters (the candidates of the row's class whose IoU with the row's box is >= bbox_vote_thresh, weighted as for the box):
+ *   TEMP_AVG (mean of the temperature-smoothed two-way probabilities), AVG (mean), IOU_AVG (IoU-weighted mean),
+ *   GENERALIZED_AVG (power mean, exponent beta), QUASI_SUM (sum / n^beta).  beta > 0 and finite (the reference's 1.0); taken
+ *   as float32.  Numerics: numpy's float32 evaluation order (pairwise sums); ID, AVG, IOU_AVG, QUASI_SUM and GENERALIZED_AVG at
+ *   beta 1 bit-exact; TEMP_AVG and GENERALIZED_AVG at beta != 1 evaluate log / exp / pow in double and round (numpy's float32
+ *   routines differ by a few ulp): within 1e-6 relative. */
+enum { DTC_VOTE_ID = 0, DTC_VOTE_TEMP_AVG, DTC_VOTE_AVG, DTC_VOTE_IOU_AVG, DTC_VOTE_GENERALIZED_AVG, DTC_VOTE_QUASI_SUM };
+typedef struct dtc_vote_scoring {
+  int32_t method;
+  float beta;
+} dtc_vote_scoring;
+
+/* Workspace of dtc_postprocess_detections_ex2; scoring == NULL or DTC_VOTE_ID: == dtc_postprocess_detections_ex_workspace_bytes.
+ * 0 for invalid arguments. */
+size_t dtc_postprocess_detections_ex2_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt,
+                                                      const dtc_vote_scoring* scoring);
+
+/* dtc_postprocess_detections_ex with the vote's scoring.  scoring == NULL or DTC_VOTE_ID: the same launches and bits as
+ * dtc_postprocess_detections_ex.  Another method needs opt->bbox_vote == 1: since the scoring rewrites the score column and the
+ * reference applies the max_det limit to the VOTED scores (:145-163), every kept row of every (class, image) segment is voted
+ * BEFORE the limit -- one more launch ahead of the limit (grid (n_cls - 1, B): a workgroup stages its segment's candidates in
+ * LDS, one wave per kept row), which replaces the kept row's score by its voted score; the limit then ranks those.  A row with
+ * no voter keeps its score (cannot happen for the reference's call: every kept row votes for itself).  Row order within a class
+ * as dtc_postprocess_detections_ex (roi ascending for hard NMS, selection order for Soft-NMS, whose voted score replaces the
+ * decayed one); the boxes are voted after the limit as with 'ID'.
+ * DTC_EINVAL: the errors of dtc_postprocess_detections_ex, a method outside 0..5, beta <= 0 or not finite, a method other than
+ * DTC_VOTE_ID without opt->bbox_vote == 1.  R <= 4096 (DTC_EUNSUPPORTED beyond), n_cls - 1 <= 256.
+ * Launches (fixed per option set, graph-capturable, no host synchronisation): dtc_postprocess_detections_ex's, + one with a
+ * scoring other than DTC_VOTE_ID. */
+int dtc_postprocess_detections_ex2(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
+                                   const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor,
+                                   const float* im_size, int batch, int max_rois, int n_cls, float wx, float wy, float ww,
+                                   float wh, float score_thresh, float nms_thresh, int max_det, const dtc_det_options* opt,
+                                   const dtc_vote_scoring* scoring, void* workspace, size_t workspace_bytes, float* dets,
+                                   int32_t* det_roi, float* det_rois_scaled, int32_t* det_count, int max_out,
+                                   const dtc_fpn_map_out* fpn, dtc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * A9  Mask resize + binarise (+ paste geometry)
  * --------------------------------------------------------------------------------------------------------------- */
@@ -419,6 +458,14 @@ int dtc_bbox_overlaps(const float* boxes, int n, int box_cols, const float* quer
  * call, where every top det is one of all_dets). */
 int dtc_box_voting(const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh,
                    float* top_dets_out, int32_t* n_voters, dtc_stream_t stream);
+
+/* box_voting(top_dets, all_dets, thresh, scoring_method, beta): dtc_box_voting, and with a scoring other than DTC_VOTE_ID
+ * (dtc_vote_scoring above) column 4 of top_dets_out holds the voted score (the top det's own score when nobody votes: the
+ * reference raises ZeroDivisionError there, n_voters reports it).  scoring == NULL or DTC_VOTE_ID: dtc_box_voting itself.
+ * One launch, one wave per top det; n_all <= 8192 (DTC_EUNSUPPORTED beyond).  DTC_EINVAL: the errors of dtc_box_voting, a
+ * method outside 0..5, beta <= 0 or not finite. */
+int dtc_box_voting_scored(const float* top_dets, int n_top, const float* all_dets, int n_all, float thresh,
+                          const dtc_vote_scoring* scoring, float* top_dets_out, int32_t* n_voters, dtc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * OUTSIDE SURVEY section 8 (the region-proposal hot path): convolution epilogue of the backbone's inference form.

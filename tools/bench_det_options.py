@@ -1,14 +1,15 @@
-"""Times the detection post-processing (dtc_postprocess_detections_ex) per option set at the bench's shape: pipeline.synthetic_batch
+"""Times the detection post-processing (dtc_postprocess_detections_ex2) per option set at the bench's shape: pipeline.synthetic_batch
 (B = 8, R = 1000, 81 classes), its class probabilities handed over as LOGITS (log p: the kernel's softmax gives p back, so the
 candidates are the bench's), rois drawn like the proposals.
 
     python tools/bench_det_options.py [--iters 100] [--warmup 20] [--host-images 8]
 
-One JSON line per mode (hard, hard+vote, linear, gaussian, linear+vote): the median of --iters launches of the whole entry (HIP
-events around each), plus the candidates per (class, image) segment (mean / max: the Soft-NMS walk is O(n^2) per segment).  Last
-line: the host-loop baseline -- what result_utils.box_results_with_nms_and_limit(do_soft_nms=True) ran before the batched path:
-the reference's 80-iteration per-class loop on the single-segment kernels (dtc_soft_nms, one launch and one copy back per
-class), reproduced below, over the same images' decoded boxes."""
+One JSON line per mode (hard, hard+vote, linear, gaussian, linear+vote, and hard+vote / linear+vote with each scoring other than 'ID':
+the vote-scoring launch ahead of the limit): the median of --iters launches of the whole entry (HIP events around each), plus the
+candidates per (class, image) segment (mean / max: the Soft-NMS walk is O(n^2) per segment).  Last lines: the host-loop baselines --
+what result_utils.box_results_with_nms_and_limit ran before the batched path, the reference's 80-iteration per-class loop on the
+single-segment kernels (one launch and one copy back per class), reproduced below, over the same images' decoded boxes: with
+do_soft_nms=True, and with hard NMS + a vote scored IOU_AVG."""
 import argparse
 import json
 import os
@@ -28,15 +29,23 @@ from detectorch_amd.utils import boxes as box_utils  # noqa: E402
 MODES = [("hard", {}), ("hard+vote", dict(do_bbox_vote=True)), ("linear", dict(do_soft_nms=True, soft_nms_method="linear")),
          ("gaussian", dict(do_soft_nms=True, soft_nms_method="gaussian")),
          ("linear+vote", dict(do_soft_nms=True, soft_nms_method="linear", do_bbox_vote=True))]
+MODES += [("%s:%s" % (name, m), dict(kw, bbox_vote_method=m)) for m in ("TEMP_AVG", "AVG", "IOU_AVG", "GENERALIZED_AVG", "QUASI_SUM")
+          for name, kw in MODES if name.endswith("+vote")]
 
 
-def host_loop(scores, boxes, num_classes=81, score_thresh=0.05, overlap_thresh=0.5):
-    """the per-class loop box_results_with_nms_and_limit(do_soft_nms=True) ran before the batched path (result_utils.py:126-165)"""
+def host_loop(scores, boxes, num_classes=81, score_thresh=0.05, overlap_thresh=0.5, vote_method=None):
+    """the per-class loop box_results_with_nms_and_limit ran before the batched path (result_utils.py:126-165): do_soft_nms=True,
+    or (vote_method) hard NMS + box_voting(scoring_method=vote_method) at 0.8"""
     cls_boxes = [[] for _ in range(num_classes)]
     for j in range(1, num_classes):
         inds = np.where(scores[:, j] > score_thresh)[0]
         dets_j = np.hstack((boxes[inds, j * 4:(j + 1) * 4], scores[inds, j][:, np.newaxis])).astype(np.float32, copy=False)
-        nms_dets, _ = box_utils.soft_nms(dets_j, sigma=0.5, overlap_thresh=overlap_thresh, score_thresh=0.0001, method="linear")
+        if vote_method is None:
+            nms_dets, _ = box_utils.soft_nms(dets_j, sigma=0.5, overlap_thresh=overlap_thresh, score_thresh=0.0001, method="linear")
+        else:
+            nms_dets = dets_j[box_utils.nms(dets_j, overlap_thresh), :]
+            if len(nms_dets):
+                nms_dets = box_utils.box_voting(nms_dets, dets_j, 0.8, scoring_method=vote_method)
         cls_boxes[j] = nms_dets
     image_scores = np.hstack([cls_boxes[j][:, -1] for j in range(1, num_classes)])
     if len(image_scores) > 100:
@@ -62,16 +71,18 @@ def main():
     cand = (probs[:, :, 1:] > 0.05).sum(1).float()                          # [B, 80] candidates per segment
     seg = dict(cand_mean=round(float(cand.mean()), 1), cand_max=int(cand.max()))
     for name, kw in MODES:
+        kw = dict(kw)
+        scoring = hip.vote_scoring(kw.pop("bbox_vote_method", "ID"))
         opt = hip.det_options(**kw)
-        ws = hip.workspace(hip.det_workspace_bytes(B, R, ncls, opt), dev)
+        ws = hip.workspace(hip.det_workspace_bytes(B, R, ncls, opt, scoring=scoring), dev)
         out = [torch.zeros((B, 128, 6), device=dev), torch.zeros((B, 128), dtype=torch.int32, device=dev),
                torch.zeros((B, 128, 4), device=dev), torch.zeros((B,), dtype=torch.int32, device=dev)]
         L, st = hip.lib(), hip.stream_ptr(dev)
 
         def launch():
-            hip.check(L.dtc_postprocess_detections_ex(rois.data_ptr(), None, logits.data_ptr(), 1, bbox.data_ptr(), None, sf.data_ptr(),
-                                                      im.data_ptr(), B, R, ncls, 10., 10., 5., 5., .05, .5, 100, opt, ws.data_ptr(),
-                                                      ws.numel(), *[t.data_ptr() for t in out], 128, None, st), name)
+            hip.check(L.dtc_postprocess_detections_ex2(rois.data_ptr(), None, logits.data_ptr(), 1, bbox.data_ptr(), None, sf.data_ptr(),
+                                                       im.data_ptr(), B, R, ncls, 10., 10., 5., 5., .05, .5, 100, opt, scoring,
+                                                       ws.data_ptr(), ws.numel(), *[t.data_ptr() for t in out], 128, None, st), name)
         for _ in range(a.warmup):
             launch()
         torch.cuda.synchronize()
@@ -90,13 +101,13 @@ def main():
     dec = [hip.bbox_transform(rois[b, :, 1:] / sf[b], bbox[b], (10., 10., 5., 5.), clip_to=(float(im[b, 0]), float(im[b, 1])))
            for b in range(n)]
     host = [(probs[b].cpu().numpy(), dec[b].cpu().numpy()) for b in range(n)]
-    host_loop(*host[0])                                                     # warm-up
-    t0 = time.perf_counter()
-    for s, bx in host:
-        host_loop(s, bx)
-    t_host = (time.perf_counter() - t0) * 1e6
-    print(json.dumps(dict(mode="host_loop_linear", images=n, total_us=round(t_host, 1), per_batch_of_8_us=round(t_host * 8 / n, 1))),
-          flush=True)
+    for mode, vm in (("host_loop_linear", None), ("host_loop_hard+vote:IOU_AVG", "IOU_AVG")):
+        host_loop(*host[0], vote_method=vm)                                 # warm-up
+        t0 = time.perf_counter()
+        for s, bx in host:
+            host_loop(s, bx, vote_method=vm)
+        t_host = (time.perf_counter() - t0) * 1e6
+        print(json.dumps(dict(mode=mode, images=n, total_us=round(t_host, 1), per_batch_of_8_us=round(t_host * 8 / n, 1))), flush=True)
 
 
 if __name__ == "__main__":
