@@ -442,6 +442,17 @@ def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w,
     return (out_boxes.view(B, nl, P, 4), out_scores.view(B, nl, P), kcnt.view(B, nl), pre_boxes, pre_scores, pre_counts)
 
 
+def collect_outputs(B, T, n_levels, dev, scores=True):
+    """The output set of dtc_fpn_collect_distribute / _kept / dtc_prepare_proposals for B images x T roi rows, in the entry points'
+    argument order: rois5 [B,T,5], roi_scores [B,T] (None without scores), roi_levels [B,T], n_out [B], rois_by_level [B,T,4],
+    level_counts [B,n_levels], idx_restore [B,T], roi_order [B,T], roi_desc [B,T,8]."""
+    f32, i32 = torch.float32, torch.int32
+    e = lambda *shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
+    return dict(rois5=e(B, T, 5), roi_scores=e(B, T) if scores else None, roi_levels=e(B, T, dtype=i32), n_out=e(B, dtype=i32),
+                rois_by_level=e(B, T, 4), level_counts=e(B, n_levels, dtype=i32), idx_restore=e(B, T, dtype=i32),
+                roi_order=e(B, T, dtype=i32), roi_desc=e(B, T, 8))
+
+
 def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max=5, inputs_sorted=False):
     """dtc_fpn_collect_distribute.  boxes [B,L,P,4], scores [B,L,P] or None, counts int32 [B,L].
     -> dict(rois5 [B,T,5], roi_scores, roi_levels [B,T], n_out [B], rois_by_level [B,T,4], level_counts [B,nl],
@@ -450,19 +461,10 @@ def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max
     boxes = boxes.contiguous()
     B, Lin, P = boxes.shape[0], boxes.shape[1], boxes.shape[2]
     T = int(post_nms_top_n)
-    nl = k_max - k_min + 1
-    f32, i32 = torch.float32, torch.int32
-    out = dict(rois5=torch.empty((B, T, 5), dtype=f32, device=dev),
-               roi_scores=torch.empty((B, T), dtype=f32, device=dev) if scores is not None else None,
-               roi_levels=torch.empty((B, T), dtype=i32, device=dev), n_out=torch.empty((B,), dtype=i32, device=dev),
-               rois_by_level=torch.empty((B, T, 4), dtype=f32, device=dev),
-               level_counts=torch.empty((B, nl), dtype=i32, device=dev),
-               idx_restore=torch.empty((B, T), dtype=i32, device=dev),
-               roi_order=torch.empty((B, T), dtype=i32, device=dev),
-               roi_desc=torch.empty((B, T, 8), dtype=f32, device=dev))
+    out = collect_outputs(B, T, k_max - k_min + 1, dev, scores=scores is not None)
     if scores is not None:
         scores = scores.contiguous()
-    counts = counts.to(i32).contiguous()
+    counts = counts.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
         rc = lib().dtc_fpn_collect_distribute(boxes.data_ptr(), _ptr(scores), counts.data_ptr(), B, Lin, P, T, k_min,
                                               k_max, out["rois5"].data_ptr(), _ptr(out["roi_scores"]),
@@ -485,14 +487,11 @@ def prepare_proposals(boxes, counts, im_scale, dedup_scale=0.0625, k_min=2, k_ma
     boxes = boxes.contiguous()
     B, N = boxes.shape[0], boxes.shape[1]
     T = int(max_out or N)
-    nl = k_max - k_min + 1
     f32, i32 = torch.float32, torch.int32
     if out is None:
-        out = dict(rois5=torch.empty((B, T, 5), dtype=f32, device=dev), roi_levels=torch.empty((B, T), dtype=i32, device=dev),
-                   n_out=torch.empty((B,), dtype=i32, device=dev), rois_by_level=torch.empty((B, T, 4), dtype=f32, device=dev),
-                   level_counts=torch.empty((B, nl), dtype=i32, device=dev), idx_restore=torch.empty((B, T), dtype=i32, device=dev),
-                   roi_order=torch.empty((B, T), dtype=i32, device=dev), roi_desc=torch.empty((B, T, 8), dtype=f32, device=dev),
-                   src_index=torch.empty((B, T), dtype=i32, device=dev))
+        out = collect_outputs(B, T, k_max - k_min + 1, dev, scores=False)
+        del out["roi_scores"]
+        out["src_index"] = torch.empty((B, T), dtype=i32, device=dev)
     counts = counts.to(i32).contiguous()
     im_scale = torch.as_tensor(im_scale, dtype=f32).to(dev).reshape(B).contiguous()
     L = lib()
@@ -519,6 +518,33 @@ def det_workspace_bytes(batch, max_rois, n_cls, opt=None, bbox_vote_method='ID',
     return need
 
 
+def _postprocess(scores, n_rois, rois5, deltas, decoded, sf, im_size, logits, weights, score_thresh, nms_thresh, max_det, max_out,
+                 ws, do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh, bbox_vote_method):
+    """dtc_postprocess_detections_ex2 on contiguous device tensors: scores [B,R,C] with either rois5 + deltas + sf + im_size (class
+    decode in the kernel; det_rois_scaled is written) or decoded boxes [B,R,4C].  -> (dets, det_roi, det_scaled or None, det_count)"""
+    dev = scores.device
+    B, R, ncls = scores.shape
+    if max_out is None:
+        max_out = 128 if max_det > 0 else R * (ncls - 1)
+    opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
+    scoring = vote_scoring(bbox_vote_method)
+    need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
+    if ws is None or ws.numel() < need:
+        ws = workspace(need, dev)
+    dets = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
+    det_roi = torch.zeros((B, max_out), dtype=torch.int32, device=dev)
+    det_scaled = torch.zeros((B, max_out, 4), dtype=torch.float32, device=dev) if decoded is None else None
+    det_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib().dtc_postprocess_detections_ex2(_ptr(rois5), _ptr(n_rois), scores.data_ptr(), 1 if logits else 0, _ptr(deltas),
+                                                  _ptr(decoded), _ptr(sf), _ptr(im_size), B, R, ncls, *[float(w) for w in weights],
+                                                  float(score_thresh), float(nms_thresh), int(max_det), opt, scoring, ws.data_ptr(),
+                                                  ws.numel(), dets.data_ptr(), det_roi.data_ptr(), _ptr(det_scaled),
+                                                  det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
+    check(rc, "dtc_postprocess_detections_ex2")
+    return dets, det_roi, det_scaled, det_count
+
+
 def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size, weights=(10., 10., 5., 5.),
                            score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None, scores_are_logits=False,
                            do_soft_nms=False, soft_nms_sigma=0.5, soft_nms_method='linear', do_bbox_vote=False,
@@ -529,31 +555,12 @@ def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, 
     bbox_vote_thresh / bbox_vote_method: the reference's options of box_results_with_nms_and_limit (result_utils.py:96-168;
     bbox_vote_method is box_voting's scoring_method, beta 1.0 as there).
     -> (dets [B,max_out,6], det_roi [B,max_out], det_rois_scaled [B,max_out,4], det_count [B])"""
-    dev = _require_cuda(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size)
-    B, R, ncls = cls_score.shape
-    if max_out is None:
-        max_out = 128 if max_det > 0 else R * (ncls - 1)
-    L_ = lib()
-    opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
-    scoring = vote_scoring(bbox_vote_method)
-    need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, dev)
-    f32, i32 = torch.float32, torch.int32
-    dets = torch.zeros((B, max_out, 6), dtype=f32, device=dev)
-    det_roi = torch.zeros((B, max_out), dtype=i32, device=dev)
-    det_scaled = torch.zeros((B, max_out, 4), dtype=f32, device=dev)
-    det_count = torch.empty((B,), dtype=i32, device=dev)
-    rois5, cls_score, bbox_pred = rois5.contiguous(), cls_score.contiguous(), bbox_pred.contiguous()
-    scaling_factor, im_size = scaling_factor.to(f32).contiguous(), im_size.to(f32).contiguous()
-    with torch.cuda.device(dev):
-        rc = L_.dtc_postprocess_detections_ex2(rois5.data_ptr(), _ptr(n_rois), cls_score.data_ptr(), 1 if scores_are_logits else 0,
-                                               bbox_pred.data_ptr(), None, scaling_factor.data_ptr(), im_size.data_ptr(), B, R, ncls,
-                                               *[float(w) for w in weights], float(score_thresh), float(nms_thresh), int(max_det),
-                                               opt, scoring, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(),
-                                               det_scaled.data_ptr(), det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections_ex2")
-    return dets, det_roi, det_scaled, det_count
+    _require_cuda(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size)
+    f32 = torch.float32
+    return _postprocess(cls_score.contiguous(), n_rois, rois5.contiguous(), bbox_pred.contiguous(), None,
+                        scaling_factor.to(f32).contiguous(), im_size.to(f32).contiguous(), scores_are_logits, weights, score_thresh,
+                        nms_thresh, max_det, max_out, ws, do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote,
+                        bbox_vote_thresh, bbox_vote_method)
 
 
 def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thresh=0.5, max_det=100, max_out=None, ws=None,
@@ -561,26 +568,10 @@ def box_results_nms_limit(scores, boxes, n_rois=None, score_thresh=0.05, nms_thr
                           bbox_vote_method='ID'):
     """box_results_with_nms_and_limit on decoded boxes (dtc_postprocess_detections_ex2 with decoded_boxes): scores [B,R,C],
     decoded boxes [B,R,4C] -> (dets [B,max_out,6], det_roi [B,max_out], det_count [B]).  Options as postprocess_detections."""
-    dev = _require_cuda(scores, boxes, n_rois)
-    B, R, ncls = scores.shape
-    if max_out is None:
-        max_out = 128 if max_det > 0 else R * (ncls - 1)
-    L_ = lib()
-    opt = det_options(do_soft_nms, soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh)
-    scoring = vote_scoring(bbox_vote_method)
-    need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, dev)
-    dets = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
-    det_roi = torch.zeros((B, max_out), dtype=torch.int32, device=dev)
-    det_count = torch.empty((B,), dtype=torch.int32, device=dev)
-    scores, boxes = scores.contiguous(), boxes.contiguous()
-    with torch.cuda.device(dev):
-        rc = L_.dtc_postprocess_detections_ex2(None, _ptr(n_rois), scores.data_ptr(), 0, None, boxes.data_ptr(), None, None, B, R,
-                                               ncls, 1., 1., 1., 1., float(score_thresh), float(nms_thresh), int(max_det), opt,
-                                               scoring, ws.data_ptr(), ws.numel(), dets.data_ptr(), det_roi.data_ptr(), None,
-                                               det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections_ex2")
+    _require_cuda(scores, boxes, n_rois)
+    dets, det_roi, _, det_count = _postprocess(scores.contiguous(), n_rois, None, None, boxes.contiguous(), None, None, False,
+                                               (1., 1., 1., 1.), score_thresh, nms_thresh, max_det, max_out, ws, do_soft_nms,
+                                               soft_nms_sigma, soft_nms_method, do_bbox_vote, bbox_vote_thresh, bbox_vote_method)
     return dets, det_roi, det_count
 
 

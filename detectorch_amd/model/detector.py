@@ -546,6 +546,24 @@ class detector(nn.Module):
         counts = torch.as_tensor(proposal_counts).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
         return proposals, counts
 
+    def _box_stages(self, path, rpn, props, feats, img_features, sf, sz, blob_hw):
+        """The middle both flavours of forward_batched share: bind the proposal inputs -- rpn = (scores, deltas) of the model's RPN
+        head (per level for FPN), or props = (boxes, counts) precomputed -- and the feature maps RoIAlign reads, launch_proposals,
+        box head -> cls / bbox, launch_detections; the head outputs stay on the path for per_image()."""
+        if props is not None:
+            path.bind_proposals(*props, sf, feats)
+        else:
+            (path.bind_rpn if self.use_fpn_body else path.bind_rpn_outputs)(*rpn, feats, scores_are_logits=self.fuse_rpn_sigmoid,
+                                                                            im_hw=blob_hw)
+        path.launch_proposals()
+        x = self._head(path.box_feats)
+        B, T = path.B, path.top_n
+        cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
+        bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
+        path.bind_heads(cls_logits, bbox_pred, sf, sz)
+        path.launch_detections()
+        path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
+
     @torch.no_grad()
     def _forward_batched_c4(self, images, sf, sz, blob_hw, det_options, proposals, proposal_counts):
         """C4 models (e2e Faster / Mask R-CNN R-50-C4, Fast R-CNN R-50-C4): res4 -> C4RegionPath stages -> res5 head -> detections
@@ -557,26 +575,14 @@ class detector(nn.Module):
         B, h, w = images.size(0), images.size(2), images.size(3)
         dev = images.device
         img_features = self.conv_body(images)                                       # res4 [B, 1024, h/16, w/16]
-        top_n = 1000
+        props = rpn = None
         if proposals is not None:
-            props, counts = self._proposal_inputs(proposals, proposal_counts, B, dev)
-            top_n = int(props.shape[1])
+            props = self._proposal_inputs(proposals, proposal_counts, B, dev)
         else:
             rpn_cls, rpn_bbox = self.rpn(img_features, logits=self.fuse_rpn_sigmoid)
-        path = self._region_path(B, h, w, dev, det_options, top_n)
-        if proposals is not None:
-            path.bind_proposals(props, counts, sf, img_features)
-        else:
-            path.bind_rpn_outputs(rpn_cls.float().contiguous(), rpn_bbox.float().contiguous(), img_features,
-                          scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
-        path.launch_proposals()
-        x = self._head(path.box_feats)                                              # res5 + avgpool: [B*T, 2048]
-        T = path.top_n
-        cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
-        bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
-        path.bind_heads(cls_logits, bbox_pred, sf, sz)
-        path.launch_detections()
-        path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
+            rpn = (rpn_cls.float().contiguous(), rpn_bbox.float().contiguous())
+        path = self._region_path(B, h, w, dev, det_options, 1000 if props is None else int(props[0].shape[1]))
+        self._box_stages(path, rpn, props, img_features, img_features, sf, sz, blob_hw)    # head: res5 + avgpool, [B*T, 2048]
         if self.use_mask_head:
             mh = self.mask_head                                                     # detector.py:99-112, the non-FPN branch
             m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(path.mask_feats))))
@@ -646,21 +652,13 @@ class detector(nn.Module):
             feats = [f.to(self.backbone_dtype) for f in feats]
             img_features = feats
         if proposals is not None:
-            props, counts = self._proposal_inputs(proposals, proposal_counts, B, dev)
-            path = self._region_path(B, h, w, dev, det_options, int(props.shape[1]))
-            path.bind_proposals(props, counts, sf, feats[:len(self.roi_spatial_scale)])
+            props = self._proposal_inputs(proposals, proposal_counts, B, dev)
+            path = self._region_path(B, h, w, dev, det_options, int(props[0].shape[1]))
+            self._box_stages(path, None, props, feats[:len(self.roi_spatial_scale)], img_features, sf, sz, blob_hw)
         else:
             path = self._region_path(B, h, w, dev, det_options)
-            path.bind_rpn([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox], feats,
-                          scores_are_logits=self.fuse_rpn_sigmoid, im_hw=blob_hw)
-        path.launch_proposals()
-        x = self._head(path.box_feats)                                              # [B*1000, 1024]
-        T = path.top_n
-        cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
-        bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
-        path.bind_heads(cls_logits, bbox_pred, sf, sz)
-        path.launch_detections()
-        path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
+            rpn = ([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox])
+            self._box_stages(path, rpn, None, feats, img_features, sf, sz, blob_hw)        # head: fc6 / fc7, [B*1000, 1024]
         if self.use_mask_head:
             mh = self.mask_head
             probs = None

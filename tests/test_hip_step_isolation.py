@@ -436,29 +436,14 @@ def test_caller_rows_past_counts_ignored(oracle, flavour, mode, fill):
 
 # ---- 3. each entry point on its own: dense call, then sparse call on the same workspace / outputs == zero-filled call -------------
 def fpn_stages(p, st):
-    from detectorch_amd import hip
-    L, ck, Bp, T, D = hip.lib(), hip.check, p.B, p.top_n, p.max_out
     return [
-        ("rpn", lambda: ck(L.dtc_rpn_topk_decode_sized(p.rpn_lv, 5, Bp, float(p.pad_h), float(p.pad_w), p.rpn_im_hw.data_ptr(), 0.0,
-                                                       p.rpn_ws.data_ptr(), p.rpn_ws.numel(), p.pre_boxes.data_ptr(),
-                                                       p.pre_scores.data_ptr(), p.pre_counts.data_ptr(), p.kmax, st), "rpn")),
-        ("nms", lambda: ck(L.dtc_nms_sorted(p.pre_boxes.data_ptr(), p.pre_counts.data_ptr(), Bp * 5, p.kmax, p.rpn_thresh, p.P,
-                                            p.nms_ws.data_ptr(), p.nms_ws.numel(), p.keep.data_ptr(), p.P, p.keep_cnt.data_ptr(),
-                                            st), "nms")),
-        ("collect", lambda: ck(L.dtc_fpn_collect_distribute_kept(
-            p.pre_boxes.data_ptr(), p.pre_scores.data_ptr(), p.kmax, p.keep.data_ptr(), p.keep_cnt.data_ptr(), p.P, Bp, 5, T, 2, 5,
-            p.rois5.data_ptr(), p.roi_scores.data_ptr(), p.roi_levels.data_ptr(), p.n_rois.data_ptr(), p.rois_by_level.data_ptr(),
-            p.level_counts.data_ptr(), p.idx_restore.data_ptr(), p.roi_order.data_ptr(), p.roi_desc.data_ptr(), st), "collect_kept")),
+        ("rpn", lambda: p._rpn_topk_decode(st)),
+        ("nms", lambda: p._nms_sorted(st)),
+        ("collect", lambda: p._collect_kept(st)),            # dtc_fpn_collect_distribute_kept
         ("box", lambda: p._roi_align_box(st)),
         (("det", "maskmap", "maskfeat"), lambda: p.launch_detections(st)),   # + the mask-branch mapping (fused or separate), mask RoIAlign
-        ("paste", lambda: ck(L.dtc_mask_paste(p.masks.data_ptr(), None, p.n_cls, p.M, p.dets.data_ptr(), p.det_count.data_ptr(),
-                                              p.im_size.data_ptr(), Bp, D, 0.5, 1, p.crops.data_ptr(), p.crop_capacity,
-                                              p.mask_boxes.data_ptr(), p.mask_rects.data_ptr(), p.mask_offsets.data_ptr(),
-                                              p.mask_bytes.data_ptr(), st), "paste")),
-        ("rle", lambda: ck(L.dtc_mask_rle(p.crops.data_ptr(), p.crop_capacity, p.mask_rects.data_ptr(), p.mask_offsets.data_ptr(),
-                                          p.det_count.data_ptr(), p.im_size.data_ptr(), Bp, D, p.rle_counts.data_ptr(),
-                                          p.rle_runs_stride, p.rle_n_runs.data_ptr(), p.rle_str.data_ptr(), p.rle_str_stride,
-                                          p.rle_str_len.data_ptr(), st), "rle")),
+        ("paste", lambda: p._mask_paste(st)),
+        ("rle", lambda: p._mask_rle(st)),
     ]
 
 
@@ -466,19 +451,10 @@ def c4_stages(p, st):
     from detectorch_amd import hip
     L, ck, Bp, T = hip.lib(), hip.check, p.B, p.top_n
     return [
-        ("rpn", lambda: ck(L.dtc_rpn_topk_decode_sized(p.rpn_lv, 1, Bp, float(p.im_h), float(p.im_w), p.rpn_im_hw.data_ptr(), 0.0,
-                                                       p.rpn_ws.data_ptr(), p.rpn_ws.numel(), p.pre_boxes.data_ptr(),
-                                                       p.pre_scores.data_ptr(), p.pre_counts.data_ptr(), p.kmax, st), "rpn")),
-        ("nms_sorted", lambda: ck(L.dtc_nms_sorted(p.pre_boxes.data_ptr(), p.pre_counts.data_ptr(), Bp, p.kmax, p.thresh, p.P,
-                                            p.nms_ws.data_ptr(), p.nms_ws.numel(), p.keep.data_ptr(), p.P, p.keep_cnt.data_ptr(),
-                                            st), "nms")),
-        ("nms", lambda: ck(L.dtc_gather_kept(p.pre_boxes.data_ptr(), p.pre_scores.data_ptr(), Bp, p.kmax, p.keep.data_ptr(),
-                                             p.keep_cnt.data_ptr(), p.P, p.prop_boxes.data_ptr(), p.prop_scores.data_ptr(), st),
-                           "gather")),
-        ("collect", lambda: ck(L.dtc_fpn_collect_distribute(
-            p.prop_boxes.data_ptr(), p.prop_scores.data_ptr(), p.keep_cnt.data_ptr(), Bp, 1, p.P, T, 4, 4, p.rois5.data_ptr(),
-            p.roi_scores.data_ptr(), p.roi_levels.data_ptr(), p.n_rois.data_ptr(), p.rois_by_level.data_ptr(),
-            p.level_counts.data_ptr(), p.idx_restore.data_ptr(), p.roi_order.data_ptr(), p.roi_desc.data_ptr(), 1, st), "collect")),
+        ("rpn", lambda: p._rpn_topk_decode(st)),
+        ("nms_sorted", lambda: p._nms_sorted(st)),
+        ("nms", lambda: p._gather_kept(st)),
+        ("collect", lambda: p._collect(st)),               # dtc_fpn_collect_distribute, inputs_sorted = 1
         ("box", lambda: p._roi_align_box(st)),             # dtc_roi_align_forward_packed_ws: the map kernel's preparation workspace
         ("det", lambda: ck(L.dtc_postprocess_detections_ex(
             p.rois5.data_ptr(), p.n_rois.data_ptr(), p.cls_score.data_ptr(), 0, p.bbox_pred.data_ptr(), None, p.sf.data_ptr(),
