@@ -894,7 +894,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   const int np2 = dtc::next_pow2(max_rois);
   const size_t smem = (size_t)np2 * sizeof(uint64_t) + (size_t)dtc::kNmsLdsCap * sizeof(float4) +
                       (size_t)((max_rois + 63) / 64) * sizeof(uint64_t);
-  if (smem > 48 * 1024) { DTC_RAISE_LDS_ONCE(dtc::det_candidates_kernel, 152 * 1024); }
+  if (smem > 48 * 1024 && dtc::raise_lds_once<dtc::det_candidates_kernel>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
   uint64_t* kept_key = reinterpret_cast<uint64_t*>(w + pl.kept_key);
   int32_t* keep_count = reinterpret_cast<int32_t*>(w + pl.keep_count);
   p.kept_key = kept_key; p.keep_count = keep_count; p.nms_thresh = nms_thresh; p.np2_max = np2;
@@ -903,7 +903,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   hipLaunchKernelGGL(dtc::det_candidates_kernel, dim3(n_cls - 1, batch), dim3(dtc::kDetThreads), smem, s, p);
   DTC_CHECK_LAUNCH();
   if (soft >= 0) {
-    DTC_RAISE_LDS_ONCE(dtc::det_soft_nms_kernel, 160 * 1024);
+    if (dtc::raise_lds_once<dtc::det_soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
     hipLaunchKernelGGL(dtc::det_soft_nms_kernel, dim3(n_cls - 1, batch), dim3(64), dtc::soft_nms_lds_bytes(max_rois), s, p,
                        opt->soft_sigma, nms_thresh, opt->soft_score_thresh, soft);
     DTC_CHECK_LAUNCH();
@@ -915,7 +915,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
     vp.kept_key = kept_key; vp.v_scores = v_scores; vp.R = max_rois; vp.n_cls = n_cls; vp.method = method;
     vp.thresh = opt->bbox_vote_thresh; vp.beta = scoring->beta;
     const size_t vsm = (size_t)max_rois * (sizeof(float4) + sizeof(float));
-    if (vsm > 48 * 1024) { DTC_RAISE_LDS_ONCE(dtc::det_vote_score_kernel, 4096 * (sizeof(float4) + sizeof(float))); }
+    if (vsm > 48 * 1024 && dtc::raise_lds_once<dtc::det_vote_score_kernel>(4096 * (sizeof(float4) + sizeof(float))) != DTC_OK) return DTC_ELAUNCH;
     hipLaunchKernelGGL(dtc::det_vote_score_kernel, dim3(n_cls - 1, batch), dim3(dtc::kVsThreads), vsm, s, vp);
     DTC_CHECK_LAUNCH();
   }
@@ -935,7 +935,7 @@ static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois
   if (cap > dtc::kFinStageMax) cap = dtc::kFinStageMax;
   const int stage_cap = (int)((cap + 3) & ~3ll);
   const size_t fsm = (size_t)stage_cap * 8;
-  if (fsm > 16 * 1024) { DTC_RAISE_LDS_ONCE(dtc::det_finalize_kernel, 116 * 1024); }      // + ~37 KB static: under the 160 KB of a CU
+  if (fsm > 16 * 1024 && dtc::raise_lds_once<dtc::det_finalize_kernel>(116 * 1024) != DTC_OK) return DTC_ELAUNCH;      // + ~37 KB static: under the 160 KB of a CU
   hipLaunchKernelGGL(dtc::det_finalize_kernel, dim3(batch), dim3(dtc::kFinThreads), fsm, s, f, stage_cap);
   DTC_CHECK_LAUNCH();
   if (vote) {

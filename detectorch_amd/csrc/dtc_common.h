@@ -27,20 +27,28 @@
     if (e__ != hipSuccess) return DTC_ELAUNCH;             \
   } while (0)
 
-// Raise a (non-template) kernel's dynamic-LDS limit once per process; thread-safe (std::call_once), the status of the one
-// hipFuncSetAttribute call is remembered, so every caller of a failed raise gets DTC_ELAUNCH.
-#define DTC_RAISE_LDS_ONCE(kernel, bytes)                                                                            \
-  do {                                                                                                               \
-    static std::once_flag once__;                                                                                    \
-    static hipError_t rc__ = hipSuccess;                                                                             \
-    std::call_once(once__, [] {                                                                                      \
-      rc__ = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 (bytes));                                                                           \
-    });                                                                                                              \
-    if (rc__ != hipSuccess) return DTC_ELAUNCH;                                                                      \
-  } while (0)
-
 namespace dtc {
+
+// Raise the dynamic-LDS limit of one or more kernels (instantiations of kernel templates included) once per process: thread-safe
+// (std::call_once), stops at the first failure, and the status is remembered, so every caller of a failed raise gets DTC_ELAUNCH.
+template <auto... Kernels>
+inline int raise_lds_once(int bytes) {
+  static std::once_flag once;
+  static hipError_t rc = hipSuccess;
+  std::call_once(once, [bytes] {
+    for (const void* k : {reinterpret_cast<const void*>(Kernels)...}) {
+      rc = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+      if (rc != hipSuccess) break;
+    }
+  });
+  return rc == hipSuccess ? DTC_OK : DTC_ELAUNCH;
+}
+
+// register vectors (two / four dwords): packed float32 arithmetic, 8- and 16-byte loads and stores
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
 __device__ __forceinline__ float fsqrt(float a) { return __fsqrt_rn(a); }
@@ -78,18 +86,16 @@ __device__ __forceinline__ float4 bf16x4_to_f32(uint2 r) {
 // Streaming (non-temporal, `nt`) stores for outputs that are written once and never re-read by the kernel that writes them: the pooled
 // features of a RoIAlign launch are 0.4-1.6 GB that would otherwise push the feature-map lines the neighbouring workgroups are about
 // to re-use out of the XCD's 4 MB L2 (round 5, box-head launch: fabric read requests -10 %, L2 hit 0.51 -> 0.54, launch -2 %).
-typedef uint32_t dtc_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t dtc_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void store_stream16(void* d, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-  const dtc_u32x4 v = {x, y, z, w};
-  __builtin_nontemporal_store(v, reinterpret_cast<dtc_u32x4*>(d));
+  const u32x4 v = {x, y, z, w};
+  __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(d));
 }
 __device__ __forceinline__ void store_stream16(void* d, float4 f) {
   store_stream16(d, __float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w));
 }
 __device__ __forceinline__ void store_stream8(void* d, uint32_t x, uint32_t y) {
-  const dtc_u32x2 v = {x, y};
-  __builtin_nontemporal_store(v, reinterpret_cast<dtc_u32x2*>(d));
+  const u32x2 v = {x, y};
+  __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(d));
 }
 
 __host__ __device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }

@@ -521,10 +521,10 @@ static int fpn_collect_launch(dtc::FpnParams p, int batch, long long n_max, dtc_
                        (p.keep ? (size_t)n_max * 4 : 0) + 16;
     if (fsm <= 150 * 1024) {
       if (R == 1) {
-        DTC_RAISE_LDS_ONCE(dtc::fpn_collect_fast_kernel<1>, 152 * 1024);
+        if (dtc::raise_lds_once<dtc::fpn_collect_fast_kernel<1>>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
         hipLaunchKernelGGL(dtc::fpn_collect_fast_kernel<1>, dim3(batch), dim3(dtc::kFpnThreads), fsm, reinterpret_cast<hipStream_t>(stream), p, (int)n_max);
       } else {
-        DTC_RAISE_LDS_ONCE(dtc::fpn_collect_fast_kernel<2>, 152 * 1024);
+        if (dtc::raise_lds_once<dtc::fpn_collect_fast_kernel<2>>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
         hipLaunchKernelGGL(dtc::fpn_collect_fast_kernel<2>, dim3(batch), dim3(dtc::kFpnThreads), fsm, reinterpret_cast<hipStream_t>(stream), p, (int)n_max);
       }
       DTC_CHECK_LAUNCH();
@@ -533,7 +533,7 @@ static int fpn_collect_launch(dtc::FpnParams p, int batch, long long n_max, dtc_
   }
   if (p.keep) return DTC_EUNSUPPORTED;         // the keep form exists in the fast kernel only: dtc_gather_kept + dtc_fpn_collect_distribute
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    DTC_RAISE_LDS_ONCE(dtc::fpn_collect_distribute_kernel, 144 * 1024);
+    if (dtc::raise_lds_once<dtc::fpn_collect_distribute_kernel>(144 * 1024) != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::fpn_collect_distribute_kernel, dim3(batch), dim3(dtc::kFpnThreads), smem,
                      reinterpret_cast<hipStream_t>(stream), p);

@@ -531,7 +531,7 @@ DTC_API int dtc_nms_sorted(const float* boxes, const int32_t* counts, int n_seg,
   // (each workgroup of the LDS walk holds ~136 KB: one per CU.  Up to 160 segments -- RPN calls up to batch 32 -- are resident
   // together; the hundreds of ~10-candidate class segments of a detection batch are better off in the one-wave kernel.)
   if (n_seg <= 160 && ncb >= 4 && ncb <= 16 && (ncb & 1) == 0 && lds_need <= 150 * 1024) {
-    if (lds_need > 48 * 1024) DTC_RAISE_LDS_ONCE(dtc::nms_reduce_lds_kernel, 152 * 1024);   // + 2 KB static
+    if (lds_need > 48 * 1024 && dtc::raise_lds_once<dtc::nms_reduce_lds_kernel>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;   // + 2 KB static
     hipLaunchKernelGGL(dtc::nms_reduce_lds_kernel, dim3(n_seg), dim3(dtc::kReduceLdsThreads), lds_need, s, mask, diag_t, counts,
                        n_stride, ncb, max_keep, keep, keep_stride, keep_count);
   } else {
@@ -551,7 +551,7 @@ DTC_API int dtc_segment_sort_desc(const float* scores, int score_stride_elems, c
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t smem = (size_t)dtc::next_pow2(n_stride) * sizeof(uint64_t);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    DTC_RAISE_LDS_ONCE(dtc::segment_sort_desc_kernel, 160 * 1024);
+    if (dtc::raise_lds_once<dtc::segment_sort_desc_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::segment_sort_desc_kernel, dim3(n_seg), dim3(dtc::kSortThreads), smem, s, scores,
                      score_stride_elems, boxes, box_stride_elems, counts, n_stride, order, sorted_boxes, sorted_scores);
@@ -588,7 +588,7 @@ DTC_API int dtc_nms(const float* dets, int n, float thresh, void* workspace, siz
   if (rc != DTC_OK) return rc;
   const size_t smem = (size_t)dtc::next_pow2(n) * sizeof(uint64_t);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    DTC_RAISE_LDS_ONCE(dtc::nms_finalize_kernel, 160 * 1024);
+    if (dtc::raise_lds_once<dtc::nms_finalize_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::nms_finalize_kernel, dim3(1), dim3(dtc::kSortThreads), smem, s, keep, cnt, order, keep_out, keep_count);
   DTC_CHECK_LAUNCH();
@@ -636,7 +636,7 @@ DTC_API int dtc_soft_nms(const float* dets, int n, float sigma, float overlap_th
   if (n > 6000) return DTC_EUNSUPPORTED;
   if (!dets || !dets_out || !inds_out) return DTC_EINVAL;
   const size_t smem = dtc::soft_nms_lds_bytes(n);
-  DTC_RAISE_LDS_ONCE(dtc::soft_nms_kernel, 160 * 1024);
+  if (dtc::raise_lds_once<dtc::soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   hipLaunchKernelGGL(dtc::soft_nms_kernel, dim3(1), dim3(64), smem, s, dets, n, sigma, overlap_thresh, score_thresh, method,
                      dets_out, inds_out, n_out);
   DTC_CHECK_LAUNCH();

@@ -614,7 +614,7 @@ DTC_API int dtc_rpn_topk_decode_sized(const dtc_rpn_level* levels, int n_levels,
   // sort_cap keys; long segments (radix sort): a second key buffer + 16 x 256 per-wave digit counters
   const size_t smem = dtc::rpn_sort_lds_bytes(sort_cap);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    DTC_RAISE_LDS_ONCE(dtc::rpn_sort_kernel, 150 * 1024);
+    if (dtc::raise_lds_once<dtc::rpn_sort_kernel>(150 * 1024) != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::rpn_sort_kernel, dim3(plan.n_seg), dim3(dtc::kSortDecodeThreads), smem, s, p, sort_cap);
   DTC_CHECK_LAUNCH();        // (a failed sort launch -- LDS over the limit -- must not be masked by the decode launch that follows)

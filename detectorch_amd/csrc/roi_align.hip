@@ -23,12 +23,11 @@
 //   roi_align_fwd_general  per-output gather; oversize pooled sizes, and the plain statement of the arithmetic
 // The default for the FPN heads (NCHW features, sampling_ratio 2) is the cluster-stationary kernel in roi_align_tile.hip,
 // for single-level inputs with adaptive sampling (the C4 heads) the map-stationary kernel in roi_align_map.hip.
-// Knobs (resolved once per process): see RoiAlignConfig below.  Variants measured slower in round 1 (wave-specialised
-// loader/compute waves, LDS-DMA staging, 16-byte row pieces, row-slot chunking, quad-aligned windows, pixel-pair loads)
-// were removed in round 2; DESIGN.md section 3.1 keeps their numbers.
+// Knobs (resolved once per process): RoiAlignKnobs in roi_align_common.h, read by roi_align_knobs() below.  DESIGN.md
+// section 3.1 keeps the numbers of the variants that measured slower (wave-specialised loader/compute waves, LDS-DMA staging,
+// 16-byte row pieces, row-slot chunking, quad-aligned windows, pixel-pair loads).
 #include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 
 #include "roi_align_common.h"
@@ -38,60 +37,77 @@ namespace dtc {
 constexpr int kRoiAlignThreads = 256;
 constexpr int kMaxTableEntries = 2048;  // PH*gh + PW*gw ; larger (adaptive sampling on a huge RoI) -> on-the-fly path
 
-// General kernel: any strides, any pooled size, adaptive sampling.  thread <-> output element (c, ph, pw) of the tile,
-// consecutive threads -> consecutive addresses of the [R,C,PH,PW] output (coalesced stores).
+// ---- what the kernels of this file share ----------------------------------------------------------------------------------
+// padding row of a fixed-shape batch (fpn.hip emits level -1): defined output
+template <typename TOut>
+__device__ __forceinline__ void zero_outputs(TOut* out, int n) {
+  for (int o = threadIdx.x; o < n; o += kRoiAlignThreads) out[o] = from_f32<TOut>(0.f);
+}
+
+// The two per-axis tables of a RoI, one behind the other: ytab[ph * gh + iy] = tab[..], xtab[pw * gw + ix] = tab[ny + ..]; lo / hi
+// multiplied by (ymul, xmul) -- 1: element indices along the axis, the element strides: offsets inside the image.
+__device__ __forceinline__ void build_axis_tables(AxisEntry* tab, const RoiHead& hd, const dtc_feat_level& L, int ny, int nx,
+                                                  int ymul = 1, int xmul = 1) {
+  for (int t = threadIdx.x; t < ny + nx; t += kRoiAlignThreads) {
+    const bool is_y = t < ny;
+    const int u = is_y ? t : t - ny, g = is_y ? hd.gh : hd.gw, mul = is_y ? ymul : xmul;
+    AxisEntry e = make_axis(is_y ? hd.sh : hd.sw, is_y ? hd.bin_h : hd.bin_w, u / g, u % g, g, is_y ? L.height : L.width);
+    e.lo *= mul; e.hi *= mul;
+    tab[t] = e;
+  }
+}
+
+// Per-output gather, the plain statement of the reference arithmetic: thread <-> output element (c, ph, pw) of the workgroup's
+// [nc, bins] slab (consecutive threads -> consecutive addresses: coalesced stores), any strides, any sampling grid.  FROM_TABLE:
+// the axis entries come from build_axis_tables(), otherwise from make_axis() on the fly (grids too large for the tables).
+// `base`: channel 0 of the slab in image hd.b.
+template <typename TIn, typename TOut, bool FROM_TABLE>
+__device__ __forceinline__ void gather_outputs(const RoiHead& hd, const dtc_feat_level& L, const AxisEntry* ytab, const AxisEntry* xtab,
+                                               const TIn* base, TOut* out, int nc, int pooled_w, int bins) {
+  const int gh = hd.gh, gw = hd.gw;
+  for (int o = threadIdx.x; o < nc * bins; o += kRoiAlignThreads) {
+    const int c = o / bins, bin = o - c * bins;
+    const int ph = bin / pooled_w, pw = bin - ph * pooled_w;
+    const TIn* d = base + (int64_t)c * L.stride_c;
+    float acc = 0.f;
+    for (int iy = 0; iy < gh; iy++) {
+      const AxisEntry y = FROM_TABLE ? ytab[ph * gh + iy] : make_axis(hd.sh, hd.bin_h, ph, iy, gh, L.height);
+      const int64_t ylo = (int64_t)y.lo * L.stride_h, yhi = (int64_t)y.hi * L.stride_h;
+      for (int ix = 0; ix < gw; ix++) {
+        const AxisEntry x = FROM_TABLE ? xtab[pw * gw + ix] : make_axis(hd.sw, hd.bin_w, pw, ix, gw, L.width);
+        const int64_t xlo = (int64_t)x.lo * L.stride_w, xhi = (int64_t)x.hi * L.stride_w;
+        const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;  // roi_align_cpu_loop.cpp:95
+        const float v1 = to_f32<TIn>(d[ylo + xlo]), v2 = to_f32<TIn>(d[ylo + xhi]);
+        const float v3 = to_f32<TIn>(d[yhi + xlo]), v4 = to_f32<TIn>(d[yhi + xhi]);
+        acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;                                // :208-211 (no contraction)
+      }
+    }
+    out[o] = from_f32<TOut>(fdiv(acc, hd.count));                                    // :216
+  }
+}
+
+// General kernel: any strides, any pooled size, adaptive sampling; one workgroup per (RoI, tile of ch_tile channels).
 template <typename TIn, typename TOut>
 __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_general(RoiAlignParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   AxisEntry* ytab = reinterpret_cast<AxisEntry*>(smem);
 
   const int c0 = blockIdx.y * p.ch_tile;
-  const RoiHead hd = load_roi_head(p, blockIdx.x);
-  const int r = hd.r, lvl = hd.lvl, b = hd.b;
-  if (lvl < 0 || lvl >= p.n_levels) {  // padding row of a fixed-shape batch (fpn.hip emits level -1): defined output
-    const int bins0 = p.pooled_h * p.pooled_w;
-    const int nc0 = min(p.ch_tile, p.channels - c0);
-    TOut* o0 = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins0;
-    for (int o = threadIdx.x; o < nc0 * bins0; o += kRoiAlignThreads) o0[o] = from_f32<TOut>(0.f);
-    return;
-  }
-  const dtc_feat_level L = p.lv[lvl];
-  const float sw = hd.sw, sh = hd.sh, bin_h = hd.bin_h, bin_w = hd.bin_w, count = hd.count;
-  const int gh = hd.gh, gw = hd.gw;
-  const int ny = p.pooled_h * gh, nx = p.pooled_w * gw;
-  const bool use_tab = (ny + nx) <= kMaxTableEntries;
-  AxisEntry* xtab = ytab + ny;
-  if (use_tab) {
-    for (int t = threadIdx.x; t < ny + nx; t += kRoiAlignThreads) {
-      if (t < ny) ytab[t] = make_axis(sh, bin_h, t / gh, t % gh, gh, L.height);
-      else { int u = t - ny; xtab[u] = make_axis(sw, bin_w, u / gw, u % gw, gw, L.width); }
-    }
-    __syncthreads();
-  }
-
-  const int bins = p.pooled_h * p.pooled_w;
   const int nc = min(p.ch_tile, p.channels - c0);
-  const TIn* base = reinterpret_cast<const TIn*>(L.data) + (int64_t)b * L.stride_n;
-  TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins;
-
-  for (int o = threadIdx.x; o < nc * bins; o += kRoiAlignThreads) {
-    const int c = o / bins, bin = o - c * bins;
-    const int ph = bin / p.pooled_w, pw = bin - ph * p.pooled_w;
-    const TIn* d = base + (int64_t)(c0 + c) * L.stride_c;
-    float acc = 0.f;
-    for (int iy = 0; iy < gh; iy++) {
-      const AxisEntry y = use_tab ? ytab[ph * gh + iy] : make_axis(sh, bin_h, ph, iy, gh, L.height);
-      const int64_t ylo = (int64_t)y.lo * L.stride_h, yhi = (int64_t)y.hi * L.stride_h;
-      for (int ix = 0; ix < gw; ix++) {
-        const AxisEntry x = use_tab ? xtab[pw * gw + ix] : make_axis(sw, bin_w, pw, ix, gw, L.width);
-        const int64_t xlo = (int64_t)x.lo * L.stride_w, xhi = (int64_t)x.hi * L.stride_w;
-        const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;  // :95
-        const float v1 = to_f32<TIn>(d[ylo + xlo]), v2 = to_f32<TIn>(d[ylo + xhi]);
-        const float v3 = to_f32<TIn>(d[yhi + xlo]), v4 = to_f32<TIn>(d[yhi + xhi]);
-        acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;                                // :208-211 (no contraction)
-      }
-    }
-    out[o] = from_f32<TOut>(fdiv(acc, count));                                       // :216
+  const int bins = p.pooled_h * p.pooled_w;
+  const RoiHead hd = load_roi_head(p, blockIdx.x);
+  TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)hd.r * p.channels + c0) * bins;
+  if (hd.lvl < 0 || hd.lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
+  const dtc_feat_level L = p.lv[hd.lvl];
+  const int ny = p.pooled_h * hd.gh, nx = p.pooled_w * hd.gw;
+  AxisEntry* xtab = ytab + ny;
+  const TIn* base = reinterpret_cast<const TIn*>(L.data) + (int64_t)hd.b * L.stride_n + (int64_t)c0 * L.stride_c;
+  if (ny + nx <= kMaxTableEntries) {
+    build_axis_tables(ytab, hd, L, ny, nx);
+    __syncthreads();
+    gather_outputs<TIn, TOut, true>(hd, L, ytab, xtab, base, out, nc, p.pooled_w, bins);
+  } else {
+    gather_outputs<TIn, TOut, false>(hd, L, ytab, xtab, base, out, nc, p.pooled_w, bins);
   }
 }
 
@@ -198,6 +214,15 @@ struct StagerNCHW {
   }
 };
 
+// four consecutive channels of a channels_last pixel as float32: one 16-byte (float32) / 8-byte (16-bit) load
+__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 load4(const __half* p) {
+  const uint2 r = *reinterpret_cast<const uint2*>(p);
+  const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
+  return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
+}
+__device__ __forceinline__ float4 load4(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
+
 template <typename TIn>
 struct StagerNHWC {
   static constexpr int U = 8;
@@ -206,13 +231,6 @@ struct StagerNHWC {
   int32_t loff[U];
   int cq, nu;         // nu = pixel rounds that contain window pixels (uniform)
   bool vec_ok;
-  static __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  static __device__ __forceinline__ float4 load4(const __half* p) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
-    return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
-  }
-  static __device__ __forceinline__ float4 load4(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
   __device__ __forceinline__ void init_window(const dtc_feat_level& L, int y0, int x0, int ww, int wh, int cts) { init(L, y0, x0, ww, wh, wh * ww, cts); }
   __device__ __forceinline__ void init(const dtc_feat_level& L, int y0, int x0, int ww, int wh, int npix, int cts) {
     const int quads = cts >> 2;
@@ -307,8 +325,6 @@ __device__ __forceinline__ void run_passes(Stager& st, LdsGeom& G, const dtc_fea
       const int bin = G.bin0 + lb;
       const int ph = bin / G.pooled_w, pw = bin - ph * G.pooled_w;
       // two channels per instruction (v_pk_mul_f32 / v_pk_add_f32: the IEEE results of the scalar forms at twice the rate)
-      typedef float f32x2 __attribute__((ext_vector_type(2)));
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
       f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
       // reference order: for iy { for ix { acc += ... } }   (roi_align_cpu_loop.cpp:203-214)
       for (int iy = 0; iy < G.gh; iy++) {
@@ -373,44 +389,19 @@ __global__ __launch_bounds__(kRoiAlignThreads, DTC_RA_WAVES) void roi_align_fwd_
   const RoiHead hd = load_roi_head(p, ri);
   const int r = hd.r, lvl = hd.lvl, b = hd.b;
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins;
-  if (lvl < 0 || lvl >= p.n_levels) {  // padding row (fpn.hip emits level -1): defined output
-    for (int o = tid; o < nc * bins; o += kRoiAlignThreads) out[o] = from_f32<TOut>(0.f);
-    return;
-  }
+  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
   const dtc_feat_level L = p.lv[lvl];
-  const float sw = hd.sw, sh = hd.sh, bin_h = hd.bin_h, bin_w = hd.bin_w, count = hd.count;
+  const float sh = hd.sh, bin_h = hd.bin_h, count = hd.count;
   const int gh = hd.gh, gw = hd.gw;
   const int ny = p.pooled_h * gh, nx = p.pooled_w * gw;
   const bool tab_ok = (ny + nx) * 4 <= kLdsTableFloats;
   AxisEntry* xtab = ytab + ny;
-  if (tab_ok) {
-    for (int t = tid; t < ny + nx; t += kRoiAlignThreads) {
-      if (t < ny) ytab[t] = make_axis(sh, bin_h, t / gh, t % gh, gh, L.height);
-      else { const int u = t - ny; xtab[u] = make_axis(sw, bin_w, u / gw, u % gw, gw, L.width); }
-    }
-  }
+  if (tab_ok) build_axis_tables(ytab, hd, L, ny, nx);
   __syncthreads();
-  const TIn* fbase = reinterpret_cast<const TIn*>(L.data) + (int64_t)b * L.stride_n;
+  const TIn* cbase = reinterpret_cast<const TIn*>(L.data) + (int64_t)b * L.stride_n + (int64_t)c0 * L.stride_c;
   if (!tab_ok) {
     // huge adaptive grid (RoI much larger than the pooled size): per-output gather, geometry on the fly
-    for (int o = tid; o < nc * bins; o += kRoiAlignThreads) {
-      const int c = o / bins, bin = o - c * bins;
-      const int ph = bin / p.pooled_w, pw = bin - ph * p.pooled_w;
-      const TIn* d = fbase + (int64_t)(c0 + c) * L.stride_c;
-      float acc = 0.f;
-      for (int iy = 0; iy < gh; iy++) {
-        const AxisEntry y = make_axis(sh, bin_h, ph, iy, gh, L.height);
-        const int64_t ylo = (int64_t)y.lo * L.stride_h, yhi = (int64_t)y.hi * L.stride_h;
-        for (int ix = 0; ix < gw; ix++) {
-          const AxisEntry x = make_axis(sw, bin_w, pw, ix, gw, L.width);
-          const int64_t xlo = (int64_t)x.lo * L.stride_w, xhi = (int64_t)x.hi * L.stride_w;
-          const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;
-          acc += w1 * to_f32<TIn>(d[ylo + xlo]) + w2 * to_f32<TIn>(d[ylo + xhi]) + w3 * to_f32<TIn>(d[yhi + xlo]) +
-                 w4 * to_f32<TIn>(d[yhi + xhi]);
-        }
-      }
-      out[o] = from_f32<TOut>(fdiv(acc, count));
-    }
+    gather_outputs<TIn, TOut, false>(hd, L, ytab, xtab, cbase, out, nc, p.pooled_w, bins);
     return;
   }
   const int y0 = ytab[0].lo, y1 = ytab[ny - 1].hi, x1 = xtab[nx - 1].hi;
@@ -447,24 +438,7 @@ __global__ __launch_bounds__(kRoiAlignThreads, DTC_RA_WAVES) void roi_align_fwd_
   }
   if (cts == 0) {
     // not even one bin row fits: per-output gather straight from global (same arithmetic)
-    for (int o = tid; o < nc * bins; o += kRoiAlignThreads) {
-      const int c = o / bins, bin = o - c * bins;
-      const int ph = bin / p.pooled_w, pw = bin - ph * p.pooled_w;
-      const TIn* d = fbase + (int64_t)(c0 + c) * L.stride_c;
-      float acc = 0.f;
-      for (int iy = 0; iy < gh; iy++) {
-        const AxisEntry y = ytab[ph * gh + iy];
-        const int64_t ylo = (int64_t)y.lo * L.stride_h, yhi = (int64_t)y.hi * L.stride_h;
-        for (int ix = 0; ix < gw; ix++) {
-          const AxisEntry x = xtab[pw * gw + ix];
-          const int64_t xlo = (int64_t)x.lo * L.stride_w, xhi = (int64_t)x.hi * L.stride_w;
-          const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;
-          acc += w1 * to_f32<TIn>(d[ylo + xlo]) + w2 * to_f32<TIn>(d[ylo + xhi]) + w3 * to_f32<TIn>(d[yhi + xlo]) +
-                 w4 * to_f32<TIn>(d[yhi + xhi]);
-        }
-      }
-      out[o] = from_f32<TOut>(fdiv(acc, count));
-    }
+    gather_outputs<TIn, TOut, true>(hd, L, ytab, xtab, cbase, out, nc, p.pooled_w, bins);
     return;
   }
   // rewrite the tables window-relative and premultiplied (in place: same entry size); a y entry is relative to the first
@@ -488,7 +462,6 @@ __global__ __launch_bounds__(kRoiAlignThreads, DTC_RA_WAVES) void roi_align_fwd_
   G.win = G.slab + cts * bins;                    // [npix + 1][cts + 4]  (cts*bins is a multiple of 4 -> 16 B aligned)
   G.cts = cts; G.bins = bins; G.gh = gh; G.gw = gw; G.pooled_w = p.pooled_w; G.nc = nc; G.count = count;
   G.inv_count = hd.inv_count;
-  const TIn* cbase = fbase + (int64_t)c0 * L.stride_c;
   const int npix_max = wh_max * ww;               // the register pipeline shape is chosen for the largest slice
   G.rows = rows; G.pooled_h = p.pooled_h; G.x0 = x0; G.ww = ww; G.y0 = y0; G.wh = wh; G.height = L.height;
   G.sh = sh; G.bin_h = bin_h; G.bin0 = 0; G.nb = bins;
@@ -525,32 +498,6 @@ __global__ __launch_bounds__(kRoiAlignThreads, DTC_RA_WAVES) void roi_align_fwd_
 // workgroup = (RoI, 64 channels); lane -> (channel quad, bin slot); results are transposed through a [64][bins] LDS slab and
 // stored as one contiguous run, exactly like the LDS kernel.  Same arithmetic, same order, bit-identical results.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename TIn> struct Vec4Load;
-template <> struct Vec4Load<float> {
-  static __device__ __forceinline__ float4 ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
-};
-template <> struct Vec4Load<__half> {
-  static __device__ __forceinline__ float4 ld(const __half* p) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
-    return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
-  }
-};
-
-template <> struct Vec4Load<bf16_t> {
-  static __device__ __forceinline__ float4 ld(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
-};
-
-// low / high 16-bit half of a dword as float32 (fp16 or bf16 element pairs of a 16-byte load)
-template <typename T> __device__ __forceinline__ float lo16_to_f32(uint32_t w);
-template <typename T> __device__ __forceinline__ float hi16_to_f32(uint32_t w);
-template <> __device__ __forceinline__ float lo16_to_f32<__half>(uint32_t w) { return __low2float(*reinterpret_cast<const __half2*>(&w)); }
-template <> __device__ __forceinline__ float hi16_to_f32<__half>(uint32_t w) { return __high2float(*reinterpret_cast<const __half2*>(&w)); }
-template <> __device__ __forceinline__ float lo16_to_f32<bf16_t>(uint32_t w) { return __uint_as_float(w << 16); }
-template <> __device__ __forceinline__ float hi16_to_f32<bf16_t>(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-template <> __device__ __forceinline__ float lo16_to_f32<float>(uint32_t w) { return 0.f; }      // never instantiated for float maps
-template <> __device__ __forceinline__ float hi16_to_f32<float>(uint32_t w) { return 0.f; }
-
 // [n_out] float32 slab -> contiguous output of type TOut: 16-byte stores where the alignment allows (4 floats, or 8 16-bit values
 // rounded exactly as from_f32 does element by element); a 2-byte store per element cost 12 x the time per byte
 template <typename TOut, int THREADS>
@@ -596,25 +543,15 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
   const RoiHead hd = load_roi_head(p, ri);
   const int r = hd.r, lvl = hd.lvl, b = hd.b;
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins;
-  if (lvl < 0 || lvl >= p.n_levels) {
-    for (int o = tid; o < nc * bins; o += kRoiAlignThreads) out[o] = from_f32<TOut>(0.f);
-    return;
-  }
+  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
   const dtc_feat_level L = p.lv[lvl];
   const float sw = hd.sw, sh = hd.sh, bin_h = hd.bin_h, bin_w = hd.bin_w, count = hd.count, inv_count = hd.inv_count;
   const int gh = hd.gh, gw = hd.gw;
   const int ny = p.pooled_h * gh, nx = p.pooled_w * gw;
   const bool tab_ok = (ny + nx) * 4 <= kLdsTableFloats;
   AxisEntry* xtab = ytab + ny;
-  if (tab_ok) {
-    // entries premultiplied by the element strides: lo/hi become element offsets inside the image
-    for (int t = tid; t < ny + nx; t += kRoiAlignThreads) {
-      AxisEntry e;
-      if (t < ny) { e = make_axis(sh, bin_h, t / gh, t % gh, gh, L.height); e.lo *= (int)L.stride_h; e.hi *= (int)L.stride_h; }
-      else { const int u = t - ny; e = make_axis(sw, bin_w, u / gw, u % gw, gw, L.width); e.lo *= (int)L.stride_w; e.hi *= (int)L.stride_w; }
-      ytab[t] = e;
-    }
-  }
+  // entries premultiplied by the element strides: lo/hi become element offsets inside the image
+  if (tab_ok) build_axis_tables(ytab, hd, L, ny, nx, (int)L.stride_h, (int)L.stride_w);
   __syncthreads();
   if constexpr (sizeof(TIn) == 2) {
     // 16-bit maps, 2 x 2 sampling grid, a full 64-channel block: lane <-> (8 channels = one 16-byte load per tap, bin slot of 32):
@@ -698,14 +635,14 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
         const AxisEntry x0e = xtab[pw * 2], x1e = xtab[pw * 2 + 1];
         const AxisEntry y0e = ytab[ph * 2], y1e = ytab[ph * 2 + 1];
         float4 t[16];
-        t[0] = Vec4Load<TIn>::ld(base + y0e.lo + x0e.lo); t[1] = Vec4Load<TIn>::ld(base + y0e.lo + x0e.hi);
-        t[2] = Vec4Load<TIn>::ld(base + y0e.hi + x0e.lo); t[3] = Vec4Load<TIn>::ld(base + y0e.hi + x0e.hi);
-        t[4] = Vec4Load<TIn>::ld(base + y0e.lo + x1e.lo); t[5] = Vec4Load<TIn>::ld(base + y0e.lo + x1e.hi);
-        t[6] = Vec4Load<TIn>::ld(base + y0e.hi + x1e.lo); t[7] = Vec4Load<TIn>::ld(base + y0e.hi + x1e.hi);
-        t[8] = Vec4Load<TIn>::ld(base + y1e.lo + x0e.lo); t[9] = Vec4Load<TIn>::ld(base + y1e.lo + x0e.hi);
-        t[10] = Vec4Load<TIn>::ld(base + y1e.hi + x0e.lo); t[11] = Vec4Load<TIn>::ld(base + y1e.hi + x0e.hi);
-        t[12] = Vec4Load<TIn>::ld(base + y1e.lo + x1e.lo); t[13] = Vec4Load<TIn>::ld(base + y1e.lo + x1e.hi);
-        t[14] = Vec4Load<TIn>::ld(base + y1e.hi + x1e.lo); t[15] = Vec4Load<TIn>::ld(base + y1e.hi + x1e.hi);
+        t[0] = load4(base + y0e.lo + x0e.lo); t[1] = load4(base + y0e.lo + x0e.hi);
+        t[2] = load4(base + y0e.hi + x0e.lo); t[3] = load4(base + y0e.hi + x0e.hi);
+        t[4] = load4(base + y0e.lo + x1e.lo); t[5] = load4(base + y0e.lo + x1e.hi);
+        t[6] = load4(base + y0e.hi + x1e.lo); t[7] = load4(base + y0e.hi + x1e.hi);
+        t[8] = load4(base + y1e.lo + x0e.lo); t[9] = load4(base + y1e.lo + x0e.hi);
+        t[10] = load4(base + y1e.hi + x0e.lo); t[11] = load4(base + y1e.hi + x0e.hi);
+        t[12] = load4(base + y1e.lo + x1e.lo); t[13] = load4(base + y1e.lo + x1e.hi);
+        t[14] = load4(base + y1e.hi + x1e.lo); t[15] = load4(base + y1e.hi + x1e.hi);
 #pragma unroll
         for (int sidx = 0; sidx < 4; sidx++) {   // (iy, ix) = (0,0) (0,1) (1,0) (1,1): the reference's accumulation order
           const AxisEntry& y = (sidx < 2) ? y0e : y1e;
@@ -725,8 +662,8 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
           const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;      // roi_align_cpu_loop.cpp:95
           float4 v1, v2, v3, v4;
           if (vec) {
-            v1 = Vec4Load<TIn>::ld(base + y.lo + x.lo); v2 = Vec4Load<TIn>::ld(base + y.lo + x.hi);
-            v3 = Vec4Load<TIn>::ld(base + y.hi + x.lo); v4 = Vec4Load<TIn>::ld(base + y.hi + x.hi);
+            v1 = load4(base + y.lo + x.lo); v2 = load4(base + y.lo + x.hi);
+            v3 = load4(base + y.hi + x.lo); v4 = load4(base + y.hi + x.hi);
           } else {
             const TIn* t1 = base + y.lo + x.lo; const TIn* t2 = base + y.lo + x.hi;
             const TIn* t3 = base + y.hi + x.lo; const TIn* t4 = base + y.hi + x.hi;
@@ -753,38 +690,45 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// Development / A-B knobs, resolved ONCE per process (thread-safe static initialisation) -- not per dispatch:
-//   DTC_ROIALIGN_TILE=0          use the RoI-stationary kernel of this file instead of the cluster-stationary one (roi_align_tile.hip)
-//   DTC_ROIALIGN_MAP=0           single-level inputs (C4) through the RoI-stationary kernel instead of the map-stationary one (roi_align_map.hip)
-//   DTC_ROIALIGN_GENERAL=1       force the per-output gather kernel (the plain statement of the arithmetic)
-//   DTC_ROIALIGN_NO_NHWC_DIRECT  channels_last features through the LDS-staged kernel
-//   DTC_RA_NO_XCD  DTC_RA_NO_CTS64
-struct RoiAlignConfig {
-  bool tile = true, map = true, general = false, nhwc_direct = true, xcd = true, cts64 = true;
-  int lds_bytes = 52 * 1024;
-};
-static const RoiAlignConfig& roi_align_config() {
-  static const RoiAlignConfig cfg = [] {
-    RoiAlignConfig c;
-    if (const char* e = getenv("DTC_ROIALIGN_TILE")) c.tile = e[0] != '0';
-    if (const char* e = getenv("DTC_ROIALIGN_MAP")) c.map = e[0] != '0';
-    c.general = getenv("DTC_ROIALIGN_GENERAL") != nullptr;
-    c.nhwc_direct = getenv("DTC_ROIALIGN_NO_NHWC_DIRECT") == nullptr;
-    c.xcd = getenv("DTC_RA_NO_XCD") == nullptr;
-    c.cts64 = getenv("DTC_RA_NO_CTS64") == nullptr;      // 64-channel sub-tiles for windows <= 128 px: +4 % on the bench workload
-    return c;
+// The one place that reads the environment for RoIAlign: every knob of RoiAlignKnobs (roi_align_common.h), each with its own
+// parse rule, resolved ONCE per process (thread-safe static initialisation) -- not per dispatch.
+const RoiAlignKnobs& roi_align_knobs() {
+  static const RoiAlignKnobs knobs = [] {
+    RoiAlignKnobs k;
+    const auto first_not_0 = [](const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; };
+    const auto is_set = [](const char* name) { return getenv(name) != nullptr; };
+    const auto number = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    const auto in_range = [&](const char* name, int lo, int hi, int dflt) { const int v = number(name, dflt); return v >= lo && v <= hi ? v : dflt; };
+    k.tile = first_not_0("DTC_ROIALIGN_TILE", true);
+    k.map = first_not_0("DTC_ROIALIGN_MAP", true);
+    k.general = is_set("DTC_ROIALIGN_GENERAL");
+    k.nhwc_direct = !is_set("DTC_ROIALIGN_NO_NHWC_DIRECT");
+    k.nhwc16 = first_not_0("DTC_RA_NHWC16", true);
+    k.nhwc_direct32 = first_not_0("DTC_RA_NHWC_DIRECT32", true);
+    k.xcd = !is_set("DTC_RA_NO_XCD");
+    k.cts64 = !is_set("DTC_RA_NO_CTS64");
+    const int cb = number("DTC_RA_TILE_CHBLOCK", 0);
+    if (cb >= 4 && (cb & 3) == 0) k.tile_ch_block = cb;
+    k.tile_cb_major = number("DTC_RA_TILE_CBMAJOR", 1) != 0;
+    k.tile_lds16_kb = in_range("DTC_RA_TILE_LDS16_KB", 36, 156, 0);
+    k.map_prep = number("DTC_RA_MAP_PREP", 1) != 0;
+    k.map_pitch = first_not_0("DTC_RA_MAP_PITCH", true);
+    k.nhwc_lds = number("DTC_RA_NHWC_LDS", 1) != 0;
+    k.nhwc_lds_kb = in_range("DTC_RA_NHWC_LDS_KB", 24, 160, 0);
+    k.nhwc_pipe = in_range("DTC_RA_NHWC_PIPE", 0, 2, 1);
+    k.nhwc_pipe16 = number("DTC_RA_NHWC_PIPE16", 0) != 0;
+    k.nhwc_lds_16bit = number("DTC_RA_NHWC_LDS_16BIT", 0) != 0;
+    return k;
   }();
-  return cfg;
+  return knobs;
 }
+
+constexpr int kLdsKernelBytes = 52 * 1024;   // dynamic LDS of a roi_align_fwd_lds workgroup: three per CU
 
 template <typename TIn, typename TOut, int CB>
 static int launch_nhwc_cb(const RoiAlignParams& p, hipStream_t stream) {
   const size_t smem = (size_t)kLdsTableFloats * 4 + (size_t)CB * p.pooled_h * p.pooled_w * 4 + 16;
-  static std::once_flag once;
-  static hipError_t rc = hipSuccess;
-  std::call_once(once, [] { rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_nhwc<TIn, TOut, CB>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-  if (rc != hipSuccess) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc<TIn, TOut, CB>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   const int nct = ceil_div(p.channels, CB);
   hipLaunchKernelGGL((roi_align_fwd_nhwc<TIn, TOut, CB>), dim3((unsigned)p.n_rois * nct), dim3(kRoiAlignThreads), smem, stream, p);
   DTC_CHECK_LAUNCH();
@@ -795,7 +739,9 @@ template <typename TIn, typename TOut>
 static int launch_nhwc(const RoiAlignParams& p, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
   // 16-bit maps with more than 64 bins (the 14 x 14 mask head): 32-channel blocks, so that the [CB][bins] float32 slab stays at 25 KB
-  if (sizeof(TIn) == 2 && p.pooled_h * p.pooled_w > 64 && p.channels % 32 == 0) return launch_nhwc_cb<TIn, TOut, 32>(p, stream);
+  if constexpr (sizeof(TIn) == 2) {
+    if (p.pooled_h * p.pooled_w > 64 && p.channels % 32 == 0) return launch_nhwc_cb<TIn, TOut, 32>(p, stream);
+  }
   // (float32 maps with 32-channel blocks -- two rounds of taps instead of four, twice the workgroups -- measured slower: 0.496 ms
   //  against 0.452 per box-head launch; float32 channels_last maps take roi_align_fwd_nhwc_lds first anyway: 0.359 ms)
   return launch_nhwc_cb<TIn, TOut, 64>(p, stream);
@@ -804,15 +750,10 @@ static int launch_nhwc(const RoiAlignParams& p, hipStream_t stream) {
 template <typename TIn, typename TOut>
 static int launch_lds(const RoiAlignParams& p, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
-  static std::once_flag once;
-  static hipError_t rc = hipSuccess;
-  std::call_once(once, [] { rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_lds<TIn, TOut>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-  if (rc != hipSuccess) return DTC_ELAUNCH;
-  const int lds_b = roi_align_config().lds_bytes;
+  if (raise_lds_once<roi_align_fwd_lds<TIn, TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   const int nct = ceil_div(p.channels, p.ch_block);
-  hipLaunchKernelGGL((roi_align_fwd_lds<TIn, TOut>), dim3((unsigned)p.n_rois * nct), dim3(kRoiAlignThreads), lds_b, stream, p,
-                     lds_b / 4);
+  hipLaunchKernelGGL((roi_align_fwd_lds<TIn, TOut>), dim3((unsigned)p.n_rois * nct), dim3(kRoiAlignThreads), kLdsKernelBytes, stream, p,
+                     kLdsKernelBytes / 4);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }
@@ -831,20 +772,12 @@ static int launch_general(const RoiAlignParams& p, hipStream_t stream) {
 }
 
 enum { kKernNhwc, kKernLds, kKernGeneral };
-template <typename TIn, typename TOut>
-static int launch_kind(int kind, const RoiAlignParams& p, hipStream_t s) {
-  return kind == kKernNhwc ? launch_nhwc<TIn, TOut>(p, s) : kind == kKernLds ? launch_lds<TIn, TOut>(p, s) : launch_general<TIn, TOut>(p, s);
-}
-// (in, out) dtype pairs: fp32 accumulate always; f16 and bf16 do not mix
 static int launch_typed(int kind, const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t s) {
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return launch_kind<float, float>(kind, p, s);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return launch_kind<__half, float>(kind, p, s);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return launch_kind<__half, __half>(kind, p, s);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F16) return launch_kind<float, __half>(kind, p, s);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return launch_kind<bf16_t, float>(kind, p, s);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return launch_kind<bf16_t, bf16_t>(kind, p, s);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_BF16) return launch_kind<float, bf16_t>(kind, p, s);
-  return DTC_EUNSUPPORTED;
+  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
+    typedef tag_type<decltype(tin)> TIn;
+    typedef tag_type<decltype(tout)> TOut;
+    return kind == kKernNhwc ? launch_nhwc<TIn, TOut>(p, s) : kind == kKernLds ? launch_lds<TIn, TOut>(p, s) : launch_general<TIn, TOut>(p, s);
+  });
 }
 
 }  // namespace dtc
@@ -856,7 +789,7 @@ static int roi_align_dispatch(const dtc_feat_level* levels, int n_levels, int ch
   if (!levels || n_levels < 1 || n_levels > DTC_MAX_LEVELS || channels < 1 || n_rois < 0 || pooled_h < 1 ||
       pooled_w < 1 || (roi_cols != 4 && roi_cols != 5) || (n_rois > 0 && ((!rois && !roi_desc) || !out)))
     return DTC_EINVAL;
-  const dtc::RoiAlignConfig& cfg = dtc::roi_align_config();
+  const dtc::RoiAlignKnobs& cfg = dtc::roi_align_knobs();
   dtc::RoiAlignParams p;
   for (int i = 0; i < n_levels; i++) {
     if (!levels[i].data || levels[i].height < 1 || levels[i].width < 1) return DTC_EINVAL;

@@ -1,6 +1,7 @@
-// Shared device helpers of the RoIAlign kernels (roi_align.hip, roi_align_tile.hip): launch parameters, the XCD-aware
-// work assignment, and the RoI geometry of roi_align_forward_loop (lib/cppcuda_cffi/src/cpp/roi_align_cpu_loop.cpp:36-173)
-// restated operation for operation so that every kernel forms bit-identical sampling positions and weights.
+// What the RoIAlign kernels (roi_align*.hip) share.  Device side: launch parameters, the XCD-aware work assignment, and the
+// RoI geometry of roi_align_forward_loop (lib/cppcuda_cffi/src/cpp/roi_align_cpu_loop.cpp:36-173) restated operation for
+// operation so that every kernel forms bit-identical sampling positions and weights.  Host side: the (input, output) dtype
+// dispatch, the A/B knob table and the launchers' declarations.
 #pragma once
 #include "dtc_common.h"
 
@@ -116,7 +117,6 @@ __device__ __forceinline__ RoiHead load_roi_head(const RoiAlignParams& p, int ri
 // {w * float(low half), w * float(high half)} of a dword of two 16-bit elements, as a register pair for the packed fp32 adds.
 // fp16: v_fma_mix_f32 converts and multiplies in ONE instruction -- fma(float(x), w, -0.0) is round(float(x) * w), the value
 // v_cvt_f32_f16 + v_mul_f32 give (adding -0 never changes a sum).  bf16: two bit operations, one v_pk_mul_f32.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <typename T> __device__ __forceinline__ f32x2 mul_pair16(uint32_t u, float w);
 template <> __device__ __forceinline__ f32x2 mul_pair16<__half>(uint32_t u, float w) {
   f32x2 r;
@@ -146,6 +146,58 @@ template <> __device__ __forceinline__ void fma_pair16<bf16_t>(f32x2& acc, uint3
   acc = __builtin_elementwise_fma(v, w2, acc);
 }
 template <> __device__ __forceinline__ void fma_pair16<float>(f32x2&, uint32_t, float) {}   // never instantiated for float maps
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// The (input, output) dtype pairs RoIAlign serves: float32 accumulation always, float32 or the map's own 16-bit type out, and a
+// float32 map may be stored as either 16-bit type; f16 and bf16 do not mix.  f(dtype_tag<TIn>, dtype_tag<TOut>) -> status.
+template <typename T> struct dtype_tag { typedef T type; };
+template <typename Tag> using tag_type = typename Tag::type;
+template <typename F>
+inline int dispatch_io_pair(int in_dtype, int out_dtype, F&& f) {
+  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return f(dtype_tag<float>{}, dtype_tag<float>{});
+  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return f(dtype_tag<__half>{}, dtype_tag<float>{});
+  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return f(dtype_tag<__half>{}, dtype_tag<__half>{});
+  if (in_dtype == DTC_F32 && out_dtype == DTC_F16) return f(dtype_tag<float>{}, dtype_tag<__half>{});
+  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return f(dtype_tag<bf16_t>{}, dtype_tag<float>{});
+  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return f(dtype_tag<bf16_t>{}, dtype_tag<bf16_t>{});
+  if (in_dtype == DTC_F32 && out_dtype == DTC_BF16) return f(dtype_tag<float>{}, dtype_tag<bf16_t>{});
+  return DTC_EUNSUPPORTED;
+}
+inline bool io_pair_supported(int in_dtype, int out_dtype) {
+  return dispatch_io_pair(in_dtype, out_dtype, [](auto, auto) { return (int)DTC_OK; }) == DTC_OK;
+}
+
+// Development / A-B knobs: environment variables that select among kernels computing the same function, read ONCE per process by
+// roi_align_knobs() (roi_align.hip; thread-safe static initialisation), none needed in production.  Every knob keeps its own
+// parse rule (the child-process tests of tests/test_hip_roi_align.py and tools/AB_KNOBS.md, which lists these fields, rely on them):
+//   "=0"   off when the value's first character is '0'         "set"  on when the variable exists, whatever its value
+//   "=n"   atoi(value); a value outside the stated range is ignored
+struct RoiAlignKnobs {
+  // which kernel roi_align_dispatch picks
+  bool tile = true;            // DTC_ROIALIGN_TILE=0: NCHW, sampling ratio 2 on the RoI-stationary LDS kernel instead of the cluster kernel
+  bool map = true;             // DTC_ROIALIGN_MAP=0: single-level inputs (C4) on the LDS kernel instead of the map-stationary kernel
+  bool general = false;        // DTC_ROIALIGN_GENERAL set: every call on the per-output gather kernel (the reference kernel's structure)
+  bool nhwc_direct = true;     // DTC_ROIALIGN_NO_NHWC_DIRECT set: channels_last maps on the LDS-staged kernel (no direct-gather / LDS-DMA kernel)
+  bool nhwc16 = true;          // DTC_RA_NHWC16=0: 16-bit channels_last maps past the grouped direct kernel (one RoI per workgroup instead)
+  bool nhwc_direct32 = true;   // DTC_RA_NHWC_DIRECT32=0: float32 channels_last maps with <= 64 bins on the LDS-DMA kernels instead
+  // work assignment and the RoI-stationary LDS kernel (roi_align.hip)
+  bool xcd = true;             // DTC_RA_NO_XCD set: work items round-robin over the XCDs
+  bool cts64 = true;           // DTC_RA_NO_CTS64 set: no 64-channel sub-tiles (they gave +4 % on the bench workload)
+  // cluster-stationary kernel (roi_align_tile.hip)
+  int tile_ch_block = 0;       // DTC_RA_TILE_CHBLOCK=n, a multiple of 4, >= 4: channels per workgroup (0: chosen per launch)
+  int tile_cb_major = 1;       // DTC_RA_TILE_CBMAJOR=n, atoi != 0: an XCD walks its groups once per channel block
+  int tile_lds16_kb = 0;       // DTC_RA_TILE_LDS16_KB=n, 36..156: LDS per workgroup on 16-bit maps (0: 38; 52: three workgroups per CU)
+  // map-stationary kernel (roi_align_map.hip)
+  bool map_prep = true;        // DTC_RA_MAP_PREP=n, off when atoi == 0: the per-launch preparation pass
+  bool map_pitch = true;       // DTC_RA_MAP_PITCH=0: LDS image rows W slots apart instead of W + 1
+  // channels_last LDS-DMA kernels (roi_align_nhwc.hip)
+  int nhwc_lds = 1;            // DTC_RA_NHWC_LDS=n, atoi != 0: 0 takes neither kernel
+  int nhwc_lds_kb = 0;         // DTC_RA_NHWC_LDS_KB=n, 24..160: LDS per workgroup (0: 40, pipelined kernel 78)
+  int nhwc_pipe = 1;           // DTC_RA_NHWC_PIPE=n, 0..2: pipelined kernel never / by bin count (> 64) / always
+  int nhwc_pipe16 = 0;         // DTC_RA_NHWC_PIPE16=n, atoi != 0: the pipelined kernel for 16-bit maps too
+  bool nhwc_lds_16bit = false; // DTC_RA_NHWC_LDS_16BIT=n, atoi != 0: the LDS-DMA kernel for 16-bit maps too
+};
+const RoiAlignKnobs& roi_align_knobs();
 
 // launchers of the cluster-stationary kernel (roi_align_tile.hip); in_dtype / out_dtype are DTC_* codes
 bool roi_align_tile_supported(const RoiAlignParams& p, int in_dtype, int out_dtype);

@@ -20,10 +20,8 @@
 //     and leave as 16-byte stores.
 // RoIs must arrive image-major (the packed descriptors of dtc_fpn_collect_distribute are); any order is CORRECT, but every
 // change of image re-stages the map.
-#include <stdlib.h>
 
 #include <atomic>
-#include <mutex>
 
 #include "roi_align_common.h"
 
@@ -36,8 +34,6 @@ constexpr int kMapThreads = 1024;
 constexpr int kMapWaves = kMapThreads / 64;
 constexpr int kMapLdsBytes = 160 * 1024 - 512;      // dynamic LDS budget (static: the rendezvous arrays)
 
-typedef float mf32x2 __attribute__((ext_vector_type(2)));
-typedef float mf32x4 __attribute__((ext_vector_type(4)));
 
 template <typename TOut> __device__ __forceinline__ void map_store4(TOut* d, float4 v);
 template <> __device__ __forceinline__ void map_store4<float>(float* d, float4 v) { store_stream16(d, v); }     // streaming stores: dtc_common.h
@@ -66,15 +62,15 @@ template <> struct MapLoad4<bf16_t> {
 // One sample of one bin: 4 taps x NQ channel quads.  ylo / yhi: byte offsets of the two rows, xlo / xhi of the two columns.
 template <int NQ>
 __device__ __forceinline__ void map_sample(const char* map, int plane_bytes, int ylo, int yhi, int xlo, int xhi, float yl,
-                                           float yh, float xl, float xh, mf32x2 (&acc)[NQ][2]) {
+                                           float yh, float xl, float xh, f32x2 (&acc)[NQ][2]) {
   const float w1 = yh * xh, w2 = yh * xl, w3 = yl * xh, w4 = yl * xl;                          // roi_align_cpu_loop.cpp:95
 #pragma unroll
   for (int q = 0; q < NQ; q++) {
     const char* m = map + q * plane_bytes;
-    const mf32x4 v1 = *reinterpret_cast<const mf32x4*>(__builtin_assume_aligned(m + ylo + xlo, 16));
-    const mf32x4 v2 = *reinterpret_cast<const mf32x4*>(__builtin_assume_aligned(m + ylo + xhi, 16));
-    const mf32x4 v3 = *reinterpret_cast<const mf32x4*>(__builtin_assume_aligned(m + yhi + xlo, 16));
-    const mf32x4 v4 = *reinterpret_cast<const mf32x4*>(__builtin_assume_aligned(m + yhi + xhi, 16));
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(m + ylo + xlo, 16));
+    const f32x4 v2 = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(m + ylo + xhi, 16));
+    const f32x4 v3 = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(m + yhi + xlo, 16));
+    const f32x4 v4 = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(m + yhi + xhi, 16));
     acc[q][0] += w1 * v1.lo + w2 * v2.lo + w3 * v3.lo + w4 * v4.lo;                               // :208-211
     acc[q][1] += w1 * v1.hi + w2 * v2.hi + w3 * v3.hi + w4 * v4.hi;
   }
@@ -293,9 +289,9 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
         const int bin = rows2 ? pm_bin : min(b0 + lane, bins - 1);        // lanes past the last bin repeat one (uniform control flow), never stored
         const bool on = rows2 ? pm_on : b0 + lane < bins;
         const int ph = (int)(((float)bin + 0.5f) * rpw), pw = bin - ph * p.pooled_w;     // bin / pooled_w, exact (bins < 2^16)
-        mf32x2 acc[NQ][2];
+        f32x2 acc[NQ][2];
 #pragma unroll
-        for (int q = 0; q < NQ; q++) { acc[q][0] = mf32x2{0.f, 0.f}; acc[q][1] = mf32x2{0.f, 0.f}; }
+        for (int q = 0; q < NQ; q++) { acc[q][0] = f32x2{0.f, 0.f}; acc[q][1] = f32x2{0.f, 0.f}; }
         if (merged) {
           // fast mode: one tap per (row, column) of the bin's footprint, weight Wy * Wx (see map_prep_kernel).  The column entries of
           // FOUR taps are fetched once (registers) and reused by every footprint row -- two wave shuffles per four taps instead of per
@@ -303,10 +299,10 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
           // channel-quad pair 2 ds_read_b128 + 4 v_pk_fma_f32 where round 5 issued 2 + 2 shuffles and 4 v_pk_mul + 4 v_pk_add.
           const int KY = gh + 1, KX = gw + 1;
           auto tap = [&](const char* m, int xo, float w) {
-            const mf32x2 wv = {w, w};
+            const f32x2 wv = {w, w};
 #pragma unroll
             for (int q = 0; q < NQ; q++) {
-              const mf32x4 v = *reinterpret_cast<const mf32x4*>(__builtin_assume_aligned(m + q * plane_bytes + xo, 16));
+              const f32x4 v = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(m + q * plane_bytes + xo, 16));
               acc[q][0] = __builtin_elementwise_fma(wv, v.lo, acc[q][0]); acc[q][1] = __builtin_elementwise_fma(wv, v.hi, acc[q][1]);
             }
           };
@@ -474,7 +470,7 @@ static int map_nq(const RoiAlignParams& p, int* use_slab, int* pitch) {
   const int H = p.lv[0].height, W = p.lv[0].width;
   const int bins = p.pooled_h * p.pooled_w;
   const bool slab_ok = bins <= 64 && (p.channels & 3) == 0;
-  static const bool pad_on = [] { const char* e = getenv("DTC_RA_MAP_PITCH"); return !(e && e[0] == '0'); }();     // A/B: DTC_RA_MAP_PITCH=0
+  const bool pad_on = roi_align_knobs().map_pitch;
   for (int nq = 2; nq >= 1; nq--) {
     if ((p.channels % (4 * nq)) != 0 && nq > 1) continue;            // whole channel groups (a tail only with single quads)
     const long long slab = slab_ok ? (long long)kMapWaves * 4 * nq * bins * 4 : 0;
@@ -495,23 +491,12 @@ bool roi_align_map_supported(const RoiAlignParams& p, int in_dtype, int out_dtyp
   if ((long long)p.n_rois * p.channels < 64 * 1024) return false;    // too little work to pay for staging whole maps
   int slab, pitch;
   if (map_nq(p, &slab, &pitch) == 0) return false;
-  const bool f = in_dtype == DTC_F32, h = in_dtype == DTC_F16, b = in_dtype == DTC_BF16;
-  return (f && (out_dtype == DTC_F32 || out_dtype == DTC_F16 || out_dtype == DTC_BF16)) ||
-         (h && (out_dtype == DTC_F32 || out_dtype == DTC_F16)) || (b && (out_dtype == DTC_F32 || out_dtype == DTC_BF16));
+  return io_pair_supported(in_dtype, out_dtype);
 }
 
 template <typename TIn, typename TOut, int NQ>
 static int launch_map_nq(const RoiAlignParams& p, int use_slab, int pitch, hipStream_t stream) {
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_map<TIn, TOut, NQ, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-    if (attr_rc == hipSuccess)
-      attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_map<TIn, TOut, NQ, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-  });
-  if (attr_rc != hipSuccess) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_map<TIn, TOut, NQ, false>, roi_align_fwd_map<TIn, TOut, NQ, true>>(kMapLdsBytes) != DTC_OK) return DTC_ELAUNCH;
   const int bins = p.pooled_h * p.pooled_w;
   const int ncg = ceil_div(p.channels, 4 * NQ);
   // runs of RoIs per workgroup: ~8 workgroups per CU over the launch (one is resident per CU), at least 8 RoIs per wave
@@ -547,14 +532,9 @@ static int launch_map_t(const RoiAlignParams& p, hipStream_t stream) {
 
 int launch_roi_align_map(const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return launch_map_t<float, float>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return launch_map_t<__half, float>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return launch_map_t<__half, __half>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F16) return launch_map_t<float, __half>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return launch_map_t<bf16_t, float>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return launch_map_t<bf16_t, bf16_t>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_BF16) return launch_map_t<float, bf16_t>(p, stream);
-  return DTC_EUNSUPPORTED;
+  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
+    return launch_map_t<tag_type<decltype(tin)>, tag_type<decltype(tout)>>(p, stream);
+  });
 }
 
 // dtc_roi_align_set_exact(): process-wide; 1 (default) = the reference's float32 operations in the reference's order, bit-identical;
@@ -567,9 +547,8 @@ size_t roi_align_map_workspace_bytes(int n_rois) { return ((size_t)(n_rois > 0 ?
 
 int launch_roi_align_map_ws(const RoiAlignParams& p0, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   RoiAlignParams p = p0;
-  static const bool no_prep = [] { const char* e = getenv("DTC_RA_MAP_PREP"); return e && atoi(e) == 0; }();   // A/B knob
   p.prep = nullptr;
-  if (workspace && !no_prep && workspace_bytes >= roi_align_map_workspace_bytes(p.n_rois) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+  if (workspace && roi_align_knobs().map_prep && workspace_bytes >= roi_align_map_workspace_bytes(p.n_rois) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
       p.pooled_h <= 64 && p.pooled_w <= 64 && (long long)p.lv[0].height * p.lv[0].width * 16 < (1ll << 30))
     p.prep = workspace;
   return launch_roi_align_map(p, in_dtype, out_dtype, stream);

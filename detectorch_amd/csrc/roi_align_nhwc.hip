@@ -20,9 +20,7 @@
 // workgroup = (RoI, 256-byte channel block); a window that does not fit the LDS image is pooled in STRIPS of bin rows; a RoI whose
 // single bin row does not fit (or a level whose strides are not the plain channels_last ones) takes the direct-gather kernel
 // roi_align_fwd_nhwc's path per output.  Results leave through an LDS slab [channels][bins] as 16-byte stores.
-#include <stdlib.h>
 
-#include <mutex>
 
 #include "roi_align_common.h"
 
@@ -33,9 +31,6 @@ constexpr int kNlChunk = 256;                  // bytes of one pixel's channel b
 constexpr int kNlMaxBins = 64;
 constexpr int kNlBinRec = 96;                  // bytes per bin record: 16 tap offsets (uint32) + y/x weights (8 floats)
 
-typedef float nf32x2 __attribute__((ext_vector_type(2)));
-typedef float nf32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t nu32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void nl_lds_void;
 typedef __attribute__((address_space(1))) const void nl_glb_void;
 
@@ -45,13 +40,13 @@ __device__ __forceinline__ int nl_uni(int v) { return __builtin_amdgcn_readfirst
 template <typename TIn> struct NlLane;
 template <> struct NlLane<float> {
   static constexpr int kCh = 4;
-  static __device__ __forceinline__ void widen(const nu32x4& r, float (&v)[4]) {
+  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[4]) {
     v[0] = __uint_as_float(r.x); v[1] = __uint_as_float(r.y); v[2] = __uint_as_float(r.z); v[3] = __uint_as_float(r.w);
   }
 };
 template <> struct NlLane<__half> {
   static constexpr int kCh = 8;
-  static __device__ __forceinline__ void widen(const nu32x4& r, float (&v)[8]) {
+  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[8]) {
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -62,7 +57,7 @@ template <> struct NlLane<__half> {
 };
 template <> struct NlLane<bf16_t> {
   static constexpr int kCh = 8;
-  static __device__ __forceinline__ void widen(const nu32x4& r, float (&v)[8]) {
+  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[8]) {
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int i = 0; i < 4; i++) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
@@ -178,9 +173,9 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
     for (int bl0 = 0; bl0 < nb; bl0 += kNlThreads / 16) {
       const int bl = bl0 + slot;
       if (bl < nb) {
-        const nu32x4* o4 = reinterpret_cast<const nu32x4*>(brec + bl * kNlBinRec);
-        const nf32x4 wy = *reinterpret_cast<const nf32x4*>(brec + bl * kNlBinRec + 64);      // yl0 yh0 yl1 yh1
-        const nf32x4 wx = *reinterpret_cast<const nf32x4*>(brec + bl * kNlBinRec + 80);      // xl0 xh0 xl1 xh1
+        const u32x4* o4 = reinterpret_cast<const u32x4*>(brec + bl * kNlBinRec);
+        const f32x4 wy = *reinterpret_cast<const f32x4*>(brec + bl * kNlBinRec + 64);      // yl0 yh0 yl1 yh1
+        const f32x4 wx = *reinterpret_cast<const f32x4*>(brec + bl * kNlBinRec + 80);      // xl0 xh0 xl1 xh1
         const float yl[2] = {wy.x, wy.z}, yh[2] = {wy.y, wy.w}, xl[2] = {wx.x, wx.z}, xh[2] = {wx.y, wx.w};
         float acc[CL];
 #pragma unroll
@@ -190,24 +185,24 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
         for (int iy = 0; iy < 2; iy++)
 #pragma unroll
           for (int ix = 0; ix < 2; ix++) {
-            const nu32x4 off = o4[iy * 2 + ix];
-            nu32x4 r1, r2, r3, r4;
+            const u32x4 off = o4[iy * 2 + ix];
+            u32x4 r1, r2, r3, r4;
             if (staged) {
-              r1 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(img32 + off.x + q * 16);
-              r2 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(img32 + off.y + q * 16);
-              r3 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(img32 + off.z + q * 16);
-              r4 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(img32 + off.w + q * 16);
+              r1 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(img32 + off.x + q * 16);
+              r2 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(img32 + off.y + q * 16);
+              r3 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(img32 + off.z + q * 16);
+              r4 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(img32 + off.w + q * 16);
             } else {
               const char* gb = reinterpret_cast<const char*>(fbase) + q * 16;
               auto ga = [&](uint32_t t) { return gb + ((int64_t)(t >> 16) * L.stride_h + (int64_t)(t & 0xffff) * L.stride_w) * (int64_t)sizeof(TIn); };
               if (dma_ok) {
-                r1 = *reinterpret_cast<const nu32x4*>(ga(off.x)); r2 = *reinterpret_cast<const nu32x4*>(ga(off.y));
-                r3 = *reinterpret_cast<const nu32x4*>(ga(off.z)); r4 = *reinterpret_cast<const nu32x4*>(ga(off.w));
+                r1 = *reinterpret_cast<const u32x4*>(ga(off.x)); r2 = *reinterpret_cast<const u32x4*>(ga(off.y));
+                r3 = *reinterpret_cast<const u32x4*>(ga(off.z)); r4 = *reinterpret_cast<const u32x4*>(ga(off.w));
               } else {      // unaligned chunks: 4-byte (2-byte) loads
                 const uint32_t* a1 = reinterpret_cast<const uint32_t*>(ga(off.x)); const uint32_t* a2 = reinterpret_cast<const uint32_t*>(ga(off.y));
                 const uint32_t* a3 = reinterpret_cast<const uint32_t*>(ga(off.z)); const uint32_t* a4 = reinterpret_cast<const uint32_t*>(ga(off.w));
-                r1 = nu32x4{a1[0], a1[1], a1[2], a1[3]}; r2 = nu32x4{a2[0], a2[1], a2[2], a2[3]};
-                r3 = nu32x4{a3[0], a3[1], a3[2], a3[3]}; r4 = nu32x4{a4[0], a4[1], a4[2], a4[3]};
+                r1 = u32x4{a1[0], a1[1], a1[2], a1[3]}; r2 = u32x4{a2[0], a2[1], a2[2], a2[3]};
+                r3 = u32x4{a3[0], a3[1], a3[2], a3[3]}; r4 = u32x4{a4[0], a4[1], a4[2], a4[3]};
               }
             }
             float v1[CL], v2[CL], v3[CL], v4[CL];
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
 }
 
 // ======================================================================================================================================
-// Round 4: the same arithmetic as a PERSISTENT, software-pipelined, wave-specialised kernel (float32 output).
+// The same arithmetic as a PERSISTENT, software-pipelined, wave-specialised kernel (float32 output).
 //
 // What bounded roi_align_fwd_nhwc_lds (counters: profiles/r04_a_*): not its fills (1.36 GB per box-head launch, 71 % of them L2 hits,
 // fabric traffic = the compulsory 0.72 + 0.40 GB) and not the LDS or the VALU -- the serial chain of a (RoI, channel block) item:
@@ -591,9 +586,9 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
           const int phl = (int)(((float)bl + 0.5f) * rpwf);
           const int pw = bl - phl * PW, ph = pa + phl;
           const NpTab ex0 = tx[2 * pw], ex1 = tx[2 * pw + 1];
-          nf32x2 acc[CL / 2];
+          f32x2 acc[CL / 2];
 #pragma unroll
-          for (int c = 0; c < CL / 2; c++) acc[c] = nf32x2{0.f, 0.f};
+          for (int c = 0; c < CL / 2; c++) acc[c] = f32x2{0.f, 0.f};
           // reference order: for iy { for ix { acc += w1*v1 + w2*v2 + w3*v3 + w4*v4 } }   (roi_align_cpu_loop.cpp:203-214)
 #pragma unroll
           for (int iy = 0; iy < 2; iy++) {
@@ -601,25 +596,25 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
 #pragma unroll
             for (int ix = 0; ix < 2; ix++) {
               const NpTab ex = ix ? ex1 : ex0;
-              nu32x4 r1, r2, r3, r4;
+              u32x4 r1, r2, r3, r4;
               if (staged) {
-                r1 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(ib + (uint32_t)(ey.off_lo + ex.off_lo));
-                r2 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(ib + (uint32_t)(ey.off_lo + ex.off_hi));
-                r3 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(ib + (uint32_t)(ey.off_hi + ex.off_lo));
-                r4 = *reinterpret_cast<__attribute__((address_space(3))) const nu32x4*>(ib + (uint32_t)(ey.off_hi + ex.off_hi));
+                r1 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(ib + (uint32_t)(ey.off_lo + ex.off_lo));
+                r2 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(ib + (uint32_t)(ey.off_lo + ex.off_hi));
+                r3 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(ib + (uint32_t)(ey.off_hi + ex.off_lo));
+                r4 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(ib + (uint32_t)(ey.off_hi + ex.off_hi));
               } else {
                 const NpRc cy = (rct + (par * 2 + 0) * kNpTabEntries)[2 * ph + iy], cx = (rct + (par * 2 + 1) * kNpTabEntries)[2 * pw + ix];
                 const NpGlb g = *reinterpret_cast<const NpGlb*>(reinterpret_cast<const char*>(ig) + par * 32);
                 const char* gb = reinterpret_cast<const char*>(g.fbase) + q * 16;
                 auto ga = [&](int yy, int xx) { return gb + ((int64_t)yy * g.sh + (int64_t)xx * g.sw) * (int64_t)sizeof(TIn); };
                 if (mode == 0) {
-                  r1 = *reinterpret_cast<const nu32x4*>(ga(cy.lo, cx.lo)); r2 = *reinterpret_cast<const nu32x4*>(ga(cy.lo, cx.hi));
-                  r3 = *reinterpret_cast<const nu32x4*>(ga(cy.hi, cx.lo)); r4 = *reinterpret_cast<const nu32x4*>(ga(cy.hi, cx.hi));
+                  r1 = *reinterpret_cast<const u32x4*>(ga(cy.lo, cx.lo)); r2 = *reinterpret_cast<const u32x4*>(ga(cy.lo, cx.hi));
+                  r3 = *reinterpret_cast<const u32x4*>(ga(cy.hi, cx.lo)); r4 = *reinterpret_cast<const u32x4*>(ga(cy.hi, cx.hi));
                 } else {      // unaligned chunks: 4-byte loads
                   const uint32_t* a1 = reinterpret_cast<const uint32_t*>(ga(cy.lo, cx.lo)); const uint32_t* a2 = reinterpret_cast<const uint32_t*>(ga(cy.lo, cx.hi));
                   const uint32_t* a3 = reinterpret_cast<const uint32_t*>(ga(cy.hi, cx.lo)); const uint32_t* a4 = reinterpret_cast<const uint32_t*>(ga(cy.hi, cx.hi));
-                  r1 = nu32x4{a1[0], a1[1], a1[2], a1[3]}; r2 = nu32x4{a2[0], a2[1], a2[2], a2[3]};
-                  r3 = nu32x4{a3[0], a3[1], a3[2], a3[3]}; r4 = nu32x4{a4[0], a4[1], a4[2], a4[3]};
+                  r1 = u32x4{a1[0], a1[1], a1[2], a1[3]}; r2 = u32x4{a2[0], a2[1], a2[2], a2[3]};
+                  r3 = u32x4{a3[0], a3[1], a3[2], a3[3]}; r4 = u32x4{a4[0], a4[1], a4[2], a4[3]};
                 }
               }
               float v1[CL], v2[CL], v3[CL], v4[CL];
@@ -628,7 +623,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
               // two channels per instruction (v_pk_mul_f32 / v_pk_add_f32: the same IEEE results, half the instructions)
 #pragma unroll
               for (int c = 0; c < CL; c += 2) {
-                const nf32x2 a1 = {v1[c], v1[c + 1]}, a2 = {v2[c], v2[c + 1]}, a3 = {v3[c], v3[c + 1]}, a4 = {v4[c], v4[c + 1]};
+                const f32x2 a1 = {v1[c], v1[c + 1]}, a2 = {v2[c], v2[c + 1]}, a3 = {v3[c], v3[c + 1]}, a4 = {v4[c], v4[c + 1]};
                 acc[c >> 1] += w1 * a1 + w2 * a2 + w3 * a3 + w4 * a4;                                                // :208-211
               }
             }
@@ -637,7 +632,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
           float* so = scr + (size_t)(q * CL) * kNpScrPitch + sl;
 #pragma unroll
           for (int c = 0; c < CL / 2; c++) {
-            const nf32x2 o = acc[c] * 0.25f;
+            const f32x2 o = acc[c] * 0.25f;
             so[(2 * c) * kNpScrPitch] = o.x; so[(2 * c + 1) * kNpScrPitch] = o.y;
           }
         }
@@ -674,21 +669,7 @@ namespace dtc {
 //                           the pipeline's fixed cost and a quarter of the bin slots busy -- so it is NOT the default there;
 //   > 64 bins (mask head)   the pipelined kernel (two 512-thread workgroups per CU, 78 KB each: two 132-pixel images): 0.129 ms per
 //                           1024-RoI launch against 0.180 for the RoI-stationary LDS kernel (roi_align.hip) that took these before.
-// Float32 output only for the pipelined kernel.  Development / A-B knobs, resolved once per process: DTC_RA_NHWC_LDS=0 (neither
-// kernel), DTC_RA_NHWC_LDS_KB, DTC_RA_NHWC_PIPE = 0 never / 1 by bin count (default) / 2 always, DTC_RA_NHWC_PIPE16=1 /
-// DTC_RA_NHWC_LDS_16BIT=1 (16-bit maps too).
-struct NlConfig { int enabled = 1, lds_kb = 0, pipe = 1, pipe16 = 0; };
-static const NlConfig& nl_config() {
-  static const NlConfig cfg = [] {
-    NlConfig c;
-    if (const char* e = getenv("DTC_RA_NHWC_LDS")) c.enabled = atoi(e) != 0;
-    if (const char* e = getenv("DTC_RA_NHWC_LDS_KB")) { const int v = atoi(e); if (v >= 24 && v <= 160) c.lds_kb = v; }
-    if (const char* e = getenv("DTC_RA_NHWC_PIPE")) { const int v = atoi(e); if (v >= 0 && v <= 2) c.pipe = v; }
-    if (const char* e = getenv("DTC_RA_NHWC_PIPE16")) c.pipe16 = atoi(e) != 0;
-    return c;
-  }();
-  return cfg;
-}
+// Float32 output only for the pipelined kernel.  Development / A-B knobs: RoiAlignKnobs::nhwc_* (roi_align_common.h).
 
 template <typename TIn> static int nl_cb() { return 16 * NlLane<TIn>::kCh; }
 
@@ -696,8 +677,8 @@ template <typename TIn> static int nl_cb() { return 16 * NlLane<TIn>::kCh; }
 struct NpPlan { int lds_b, img_pixels, wgs_per_cu; };
 static bool np_plan(int in_dtype, NpPlan& pl) {
   const int cb = in_dtype == DTC_F32 ? 64 : 128;
-  const NlConfig& cfg = nl_config();
-  pl.lds_b = (cfg.lds_kb ? cfg.lds_kb : 78) * 1024;
+  const RoiAlignKnobs& cfg = roi_align_knobs();
+  pl.lds_b = (cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 78) * 1024;
   const int room = pl.lds_b - kNpHdrBytes - kNpPoolWaves * cb * kNpScrPitch * 4;
   pl.img_pixels = room < 0 ? 0 : ((room / 2 / kNlChunk) & ~3);       // two images; the DMA writes whole groups of 4 pixels
   if (pl.img_pixels > 8188) pl.img_pixels = 8188;                     // pixel indices stay exact in the float reciprocal
@@ -707,28 +688,25 @@ static bool np_plan(int in_dtype, NpPlan& pl) {
   return pl.img_pixels >= 16;
 }
 static bool np_takes(int bins, int in_dtype, int out_dtype) {
-  const NlConfig& cfg = nl_config();
-  return (cfg.pipe == 2 || (cfg.pipe == 1 && bins > kNlMaxBins)) && out_dtype == DTC_F32 && (in_dtype == DTC_F32 || cfg.pipe16);
+  const RoiAlignKnobs& cfg = roi_align_knobs();
+  return (cfg.nhwc_pipe == 2 || (cfg.nhwc_pipe == 1 && bins > kNlMaxBins)) && out_dtype == DTC_F32 && (in_dtype == DTC_F32 || cfg.nhwc_pipe16);
 }
 
 bool roi_align_nhwc_lds_supported(const RoiAlignParams& p, int in_dtype, int out_dtype) {
-  const NlConfig& cfg = nl_config();
-  if (!cfg.enabled || p.sampling_ratio != 2) return false;
+  const RoiAlignKnobs& cfg = roi_align_knobs();
+  if (!cfg.nhwc_lds || p.sampling_ratio != 2) return false;
   // 16-bit maps: the direct-gather kernel (8-channel lanes, roi_align.hip) unless asked
-  static const bool force16 = [] { const char* e = getenv("DTC_RA_NHWC_LDS_16BIT"); return e && atoi(e) != 0; }();
-  if (in_dtype != DTC_F32 && !force16 && !cfg.pipe16) return false;
+  if (in_dtype != DTC_F32 && !cfg.nhwc_lds_16bit && !cfg.nhwc_pipe16) return false;
   const int bins = p.pooled_h * p.pooled_w;
   if (p.pooled_h > 16 || p.pooled_w > 16) return false;
   const int cb = in_dtype == DTC_F32 ? 64 : 128;
   if (p.channels % cb != 0) return false;
   if (np_takes(bins, in_dtype, out_dtype)) { NpPlan pl; if (!np_plan(in_dtype, pl)) return false; }
-  // the round-3 kernel: <= 64 bins; the tables and the output slab must leave room for a window image (else: the direct-gather kernel)
-  else if (bins > kNlMaxBins || ((cfg.lds_kb ? cfg.lds_kb : 40) * 1024 - (1024 + kNlMaxBins * kNlBinRec + cb * bins * 4)) / kNlChunk < 16 + 3) return false;
+  // roi_align_fwd_nhwc_lds: <= 64 bins; the tables and the output slab must leave room for a window image (else: the direct-gather kernel)
+  else if (bins > kNlMaxBins || ((cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 40) * 1024 - (1024 + kNlMaxBins * kNlBinRec + cb * bins * 4)) / kNlChunk < 16 + 3) return false;
   for (int l = 0; l < p.n_levels; l++)
     if (p.lv[l].stride_c != 1 || p.lv[l].height > 65535 || p.lv[l].width > 65535) return false;
-  const bool f = in_dtype == DTC_F32, h = in_dtype == DTC_F16, b = in_dtype == DTC_BF16;
-  return (f && (out_dtype == DTC_F32 || out_dtype == DTC_F16 || out_dtype == DTC_BF16)) ||
-         (h && (out_dtype == DTC_F32 || out_dtype == DTC_F16)) || (b && (out_dtype == DTC_F32 || out_dtype == DTC_BF16));
+  return io_pair_supported(in_dtype, out_dtype);
 }
 
 static int np_cus() {      // compute units of the device the launch goes to (MI355X: 256 = 8 XCDs x 32)
@@ -742,16 +720,7 @@ static int np_cus() {      // compute units of the device the launch goes to (MI
 
 template <typename TIn>
 static int launch_np_t(const RoiAlignParams& p, int in_dtype, hipStream_t stream) {
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_nhwc_pipe<TIn, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_rc == hipSuccess)
-      attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_nhwc_pipe<TIn, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  if (attr_rc != hipSuccess) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc_pipe<TIn, true>, roi_align_fwd_nhwc_pipe<TIn, false>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   NpPlan pl;
   if (!np_plan(in_dtype, pl)) return DTC_EUNSUPPORTED;
   const int cb = nl_cb<TIn>();
@@ -772,17 +741,11 @@ static int launch_np_t(const RoiAlignParams& p, int in_dtype, hipStream_t stream
 
 template <typename TIn, typename TOut>
 static int launch_nl_t(const RoiAlignParams& p, hipStream_t stream) {
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_nhwc_lds<TIn, TOut>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  if (attr_rc != hipSuccess) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc_lds<TIn, TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   const int bins = p.pooled_h * p.pooled_w;
   const int cb = nl_cb<TIn>();
   const int fixed = 1024 + kNlMaxBins * kNlBinRec + cb * bins * 4;
-  const int lds_b = (nl_config().lds_kb ? nl_config().lds_kb : 40) * 1024;
+  const int lds_b = (roi_align_knobs().nhwc_lds_kb ? roi_align_knobs().nhwc_lds_kb : 40) * 1024;
   int img_pixels = ((lds_b - fixed) / kNlChunk) & ~3;           // the DMA writes whole groups of 4 pixels
   if (img_pixels < 16) return DTC_EUNSUPPORTED;
   if (img_pixels > 8188) img_pixels = 8188;                      // pixel indices stay exact in the float reciprocal
@@ -800,14 +763,9 @@ int launch_roi_align_nhwc_lds(const RoiAlignParams& p, int in_dtype, int out_dty
     if (in_dtype == DTC_BF16) return launch_np_t<bf16_t>(p, in_dtype, stream);
     return DTC_EUNSUPPORTED;
   }
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return launch_nl_t<float, float>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F16) return launch_nl_t<float, __half>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_BF16) return launch_nl_t<float, bf16_t>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return launch_nl_t<__half, float>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return launch_nl_t<__half, __half>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return launch_nl_t<bf16_t, float>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return launch_nl_t<bf16_t, bf16_t>(p, stream);
-  return DTC_EUNSUPPORTED;
+  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
+    return launch_nl_t<tag_type<decltype(tin)>, tag_type<decltype(tout)>>(p, stream);
+  });
 }
 
 }  // namespace dtc

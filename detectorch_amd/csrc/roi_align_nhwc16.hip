@@ -309,14 +309,6 @@ __global__ __launch_bounds__(kN16Threads) void roi_align_fwd_nhwc16(RoiAlignPara
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static bool n16_enabled() {      // A/B: DTC_RA_NHWC16=0 sends 16-bit channels_last launches to roi_align_fwd_nhwc (one RoI per workgroup)
-  static const bool on = [] { const char* e = getenv("DTC_RA_NHWC16"); return !(e && e[0] == '0'); }();
-  return on;
-}
-static bool n16_f32() {          // DTC_RA_NHWC_DIRECT32=0: float32 channels_last maps with <= 64 bins stay on the LDS-DMA kernels (roi_align_nhwc.hip)
-  static const bool on = [] { const char* e = getenv("DTC_RA_NHWC_DIRECT32"); return !(e && e[0] == '0'); }();
-  return on;
-}
 static int n16_out_size(int out_dtype) { return out_dtype == DTC_F32 ? 4 : 2; }
 static int n16_cb(const RoiAlignParams& p, int out_dtype) {
   const long long per64 = 64ll * p.pooled_h * p.pooled_w * n16_out_size(out_dtype);
@@ -324,11 +316,11 @@ static int n16_cb(const RoiAlignParams& p, int out_dtype) {
 }
 
 bool roi_align_nhwc16_supported(const RoiAlignParams& p, int in_dtype, int out_dtype) {
-  if (!n16_enabled() || p.sampling_ratio != 2 || p.n_rois < 1) return false;
+  if (!roi_align_knobs().nhwc16 || p.sampling_ratio != 2 || p.n_rois < 1) return false;
   // float32 maps: 4-channel lanes.  Measured against the LDS-DMA kernels (tools/r04/README.md section 6): box head 0.375 against 0.393 ms on
   // the bench RoIs and 0.40 against 0.51 on the harder set (no window to stage: the cost does not depend on the RoI size); the
   // 14 x 14 mask head 0.148 against 0.130 -> taken for <= 64 bins only
-  if (in_dtype == DTC_F32) { if (!n16_f32() || out_dtype != DTC_F32 || p.pooled_h * p.pooled_w > 64) return false; }
+  if (in_dtype == DTC_F32) { if (!roi_align_knobs().nhwc_direct32 || out_dtype != DTC_F32 || p.pooled_h * p.pooled_w > 64) return false; }
   else if (in_dtype != DTC_F16 && in_dtype != DTC_BF16) return false;
   if (out_dtype != DTC_F32 && out_dtype != in_dtype) return false;
   const int epl = in_dtype == DTC_F32 ? 4 : 8;          // elements per 16-byte load
@@ -370,12 +362,13 @@ static int launch_n16_cb(const RoiAlignParams& p, int cb, hipStream_t stream) {
 
 int launch_roi_align_nhwc16(const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
   const int cb = n16_cb(p, out_dtype);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return launch_n16_cb<float, float>(p, cb, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return launch_n16_cb<__half, __half>(p, cb, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return launch_n16_cb<__half, float>(p, cb, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return launch_n16_cb<bf16_t, bf16_t>(p, cb, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return launch_n16_cb<bf16_t, float>(p, cb, stream);
-  return DTC_EINVAL;
+  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
+    typedef tag_type<decltype(tin)> TIn;
+    typedef tag_type<decltype(tout)> TOut;
+    // a float32 map is served with float32 output only (roi_align_nhwc16_supported): no kernel for the other two pairs
+    if constexpr (sizeof(TIn) == 4 && sizeof(TOut) == 2) return (int)DTC_EUNSUPPORTED;
+    else return launch_n16_cb<TIn, TOut>(p, cb, stream);
+  });
 }
 
 }  // namespace dtc

@@ -30,9 +30,7 @@
 // Anything the cluster path does not cover takes a correct slow path inside the same kernel: levels whose rows are not
 // 16-byte aligned (P5: 42 columns) are staged with unaligned pieces or clamped scalar loads; a single RoI whose window exceeds
 // the LDS image is gathered per output straight from global memory; padding rows (level < 0) are zero-filled.
-#include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 
 #include "roi_align_common.h"
@@ -62,10 +60,6 @@ enum { kGrpPool = 0, kGrpZero = 1, kGrpAbsent = 2, kGrpGather = 3 };
 // 16-byte (fp32) / 8-byte (fp16, bf16) row pieces through raw buffer loads: SGPR resource (base of this cluster's image /
 // channel block) + 32-bit lane offset + SGPR pass offset -- no 64-bit address registers, and dword alignment is enough
 // (rows of a level whose width is not a multiple of 4, P5's 42 columns, are read with the same instruction).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void* base) {
   // raw buffer, no bounds clamp (num_records = 2^32 - 1); word 3 = DATA_FORMAT 32 (the gfx9 raw-buffer encoding)
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xffffffff, 0x00020000);
@@ -706,55 +700,34 @@ namespace dtc {
 #endif
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct TileConfig {
-  int nt = 256;        // threads per workgroup
-  int lds_kb = 0;      // LDS per workgroup (0: TileShape<NT>::kLdsKB)
-  int lds16_kb = 0;    // ... for 16-bit maps (their LDS image is half the size)
-  int k = 0;           // RoIs per workgroup (0: threads / bins)
-  int ch_block = 0;    // channels per workgroup (0: chosen per launch)
-  int merge_pct = 250; // a cluster may stage at most this % of the pixels its members would stage separately
-  int nq_cap = 0;      // channel quads per pass, upper bound (0: 4) -- sizes the LDS output slab
-  int reverse = 1;     // walk an XCD's slice of the visiting order back to front (heaviest workgroups first)
-  int cb_major = 1;    // an XCD walks its groups once per channel block
-};
-static const TileConfig& tile_config() {   // A/B knobs (DTC_RA_TILE_CHBLOCK, DTC_RA_TILE_CBMAJOR, DTC_RA_TILE_LDS16_KB), resolved ONCE (thread-safe static initialisation)
-  static const TileConfig cfg = [] {
-    TileConfig c;
-    if (const char* e = getenv("DTC_RA_TILE_CBMAJOR")) c.cb_major = atoi(e) != 0;
-    if (const char* e = getenv("DTC_RA_TILE_LDS16_KB")) { const int v = atoi(e); if (v >= 36 && v <= 156) c.lds16_kb = v; }
-    if (const char* e = getenv("DTC_RA_TILE_CHBLOCK")) { const int v = atoi(e); if (v >= 4 && (v & 3) == 0) c.ch_block = v; }
-    return c;
-  }();
-  return cfg;
-}
+// launch shape that no knob changes (the knobs: RoiAlignKnobs::tile_*, roi_align_common.h)
+constexpr int kTileThreads = 256;    // threads per workgroup
+constexpr int kTileMergePct = 250;   // a cluster may stage at most this % of the pixels its members would stage separately
+constexpr int kTileNqCap = 4;        // channel quads per pass, upper bound -- sizes the LDS output slab
+constexpr int kTileReverse = 1;      // walk an XCD's slice of the visiting order back to front (heaviest workgroups first)
 
 template <typename TIn, typename TOut, int NT, bool FUSED>
 static int launch_tile_nt(RoiAlignParams p, hipStream_t stream) {
-  const TileConfig& cfg = tile_config();
+  const RoiAlignKnobs& cfg = roi_align_knobs();
   const int bins = p.pooled_h * p.pooled_w;
-  int K = cfg.k ? cfg.k : NT / bins;
+  int K = NT / bins;               // RoIs per workgroup
   K = K < 1 ? 1 : (K > kTileMaxK ? kTileMaxK : K);
   if (K * bins > NT) K = NT / bins;
   if (K < 1) return DTC_EUNSUPPORTED;
-  const int lds_b = (sizeof(TIn) == 2 ? (cfg.lds16_kb ? cfg.lds16_kb : TileShape<NT>::kLds16KB) : cfg.lds_kb ? cfg.lds_kb : TileShape<NT>::kLdsKB) * 1024;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_align_fwd_tile<TIn, TOut, NT, FUSED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  if (attr_rc != hipSuccess) return DTC_ELAUNCH;
-  const int nq_cap = cfg.nq_cap ? cfg.nq_cap : 4;
+  // 16-bit maps: their LDS image is half the size
+  const int lds_b = (sizeof(TIn) == 2 ? (cfg.tile_lds16_kb ? cfg.tile_lds16_kb : TileShape<NT>::kLds16KB) : TileShape<NT>::kLdsKB) * 1024;
+  if (raise_lds_once<roi_align_fwd_tile<TIn, TOut, NT, FUSED>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  const int nq_cap = kTileNqCap;
   if (kTileHdrBytes + K * bins * 16 * nq_cap + 20 * 1024 > lds_b) return DTC_EUNSUPPORTED;
   const int ngrp = ceil_div(p.n_rois, K);
   // channels per workgroup: the per-cluster setup (geometry, item registers) is paid once per block; keep >= ~4 workgroups per CU
   // measured on MI355X: 8000 RoIs x 256 ch (1600 groups): 32 -> 0.48, 64 -> 0.41, 128 -> 0.42 ms; 16 000 RoIs fp16 (3200 groups):
   // 64 -> 0.568, 128 -> 0.545 ms -- the larger block as soon as it still leaves ~8 workgroups per slot
-  int cb = cfg.ch_block ? cfg.ch_block : ((long long)ngrp * ceil_div(p.channels, 128) >= 6144 ? 128 : 64);
-  while (!cfg.ch_block && cb > 32 && (long long)ngrp * ceil_div(p.channels, cb) < 2048) cb >>= 1;
+  int cb = cfg.tile_ch_block ? cfg.tile_ch_block : ((long long)ngrp * ceil_div(p.channels, 128) >= 6144 ? 128 : 64);
+  while (!cfg.tile_ch_block && cb > 32 && (long long)ngrp * ceil_div(p.channels, cb) < 2048) cb >>= 1;
   p.ch_block = cb;
   const int nct = ceil_div(p.channels, p.ch_block);
-  hipLaunchKernelGGL((roi_align_fwd_tile<TIn, TOut, NT, FUSED>), dim3((unsigned)ngrp * nct), dim3(NT), lds_b, stream, p, K, lds_b, nq_cap, cfg.merge_pct, (cfg.reverse ? 1 : 0) | (p.xcd_remap ? 0 : 2) | (cfg.cb_major ? 4 : 0));
+  hipLaunchKernelGGL((roi_align_fwd_tile<TIn, TOut, NT, FUSED>), dim3((unsigned)ngrp * nct), dim3(NT), lds_b, stream, p, K, lds_b, nq_cap, kTileMergePct, (kTileReverse ? 1 : 0) | (p.xcd_remap ? 0 : 2) | (cfg.tile_cb_major ? 4 : 0));
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }
@@ -762,28 +735,21 @@ static int launch_tile_nt(RoiAlignParams p, hipStream_t stream) {
 template <typename TIn, typename TOut>
 static int launch_tile_t(const RoiAlignParams& p, hipStream_t stream) {
   // 16-bit maps in contract mode (dtc_roi_align_set_exact(0), read at launch time like the C4 kernel's fast mode): fused pooling
-  if constexpr (sizeof(TIn) == 2) { if (!roi_align_get_exact()) return launch_tile_nt<TIn, TOut, 256, true>(p, stream); }
-  return launch_tile_nt<TIn, TOut, 256, false>(p, stream);
+  if constexpr (sizeof(TIn) == 2) { if (!roi_align_get_exact()) return launch_tile_nt<TIn, TOut, kTileThreads, true>(p, stream); }
+  return launch_tile_nt<TIn, TOut, kTileThreads, false>(p, stream);
 }
 
 bool roi_align_tile_supported(const RoiAlignParams& p, int in_dtype, int out_dtype) {
   if (p.sampling_ratio != 2) return false;
-  if (p.pooled_h * p.pooled_w > tile_config().nt) return false;
-  const bool f = in_dtype == DTC_F32, h = in_dtype == DTC_F16, b = in_dtype == DTC_BF16;
-  return (f && (out_dtype == DTC_F32 || out_dtype == DTC_F16 || out_dtype == DTC_BF16)) ||
-         (h && (out_dtype == DTC_F32 || out_dtype == DTC_F16)) || (b && (out_dtype == DTC_F32 || out_dtype == DTC_BF16));
+  if (p.pooled_h * p.pooled_w > kTileThreads) return false;
+  return io_pair_supported(in_dtype, out_dtype);
 }
 
 int launch_roi_align_tile(const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F32) return launch_tile_t<float, float>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F32) return launch_tile_t<__half, float>(p, stream);
-  if (in_dtype == DTC_F16 && out_dtype == DTC_F16) return launch_tile_t<__half, __half>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_F16) return launch_tile_t<float, __half>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_F32) return launch_tile_t<bf16_t, float>(p, stream);
-  if (in_dtype == DTC_BF16 && out_dtype == DTC_BF16) return launch_tile_t<bf16_t, bf16_t>(p, stream);
-  if (in_dtype == DTC_F32 && out_dtype == DTC_BF16) return launch_tile_t<float, bf16_t>(p, stream);
-  return DTC_EUNSUPPORTED;
+  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
+    return launch_tile_t<tag_type<decltype(tin)>, tag_type<decltype(tout)>>(p, stream);
+  });
 }
 
 }  // namespace dtc

@@ -157,6 +157,36 @@ def test_ragged_channel_counts_and_shapes(hip, oracle, C, layout):
         assert np.array_equal(out, ref), (C, layout, H, W, ph, pw, sr)
 
 
+_GATHER_CASES = {
+    # adaptive grids 150 x 150 and 144 x 15: 600 and 318 axis-table entries against the LDS kernel's 256 -> geometry on the fly;
+    # the third RoI (20 entries) takes the table
+    "lds_on_the_fly": (40, 40, 2, [[0, 0, 300, 300], [5, 3, 35, 290], [10, 10, 20, 20]]),
+    # 529 bins are past the LDS kernel's slab -> roi_align_fwd_general; 2208 and 2277 entries exceed its 2048, 92 do not
+    "general_oversize": (64, 48, 23, [[0, 0, 1100, 1100], [-20, -30, 1000, 1200], [3, 3, 40, 30]]),
+    # 200 and 150 entries fit the table, but one bin row's window (about 51 x 101 pixels) is past the 1024 the stagers hold
+    "lds_window_too_large": (110, 110, 2, [[0, 0, 100, 100], [4, 7, 99, 60]]),
+}
+
+
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+@pytest.mark.parametrize("case", sorted(_GATHER_CASES))
+def test_per_output_gather_fallbacks_vs_oracle(hip, oracle, case, layout):
+    """The per-output gather of roi_align.hip at its three call sites: adaptive sampling grids too large for the axis tables
+    (geometry formed on the fly, in the LDS-staged and in the general kernel) and a window of which not even one bin row fits
+    LDS (gather from the tables).  Single level, spatial_scale 1, 3 channels, batch 2; bit-equal to the oracle."""
+    H, W, ph, boxes = _GATHER_CASES[case]
+    rs = synth.rng(1, 900 + H)
+    feat = rs.standard_normal((2, 3, H, W)).astype(np.float32)
+    rois5 = np.array([[i % 2] + b for i, b in enumerate(boxes)], np.float32)
+    ref = oracle.roi_align_forward(feat, rois5, ph, ph, 1.0, 0)
+    f = cu(feat)
+    if layout == "nhwc":
+        f = f.contiguous(memory_format=torch.channels_last)
+    out = hip.roi_align_forward(f, 1.0, cu(rois5), ph, ph, 0).cpu().numpy()
+    assert np.isfinite(ref).all() and np.abs(ref).max() > 0
+    assert np.array_equal(out, ref), (case, layout, np.abs(out - ref).max())
+
+
 def test_ordered_and_packed_entry_points(hip, oracle):
     feats, rois5, lv, ref = _fpn_case(oracle, 200, 16, 7, 2, 4242, batch=2)
     tf = [cu(f) for f in feats]
