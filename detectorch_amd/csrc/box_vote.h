@@ -9,6 +9,7 @@
 // reduction of the [m,4] product), the weight sum is numpy's pairwise float32 summation.
 #pragma once
 #include "dtc_common.h"
+#include "wave_ops.h"
 
 namespace dtc {
 
@@ -79,7 +80,7 @@ __device__ __forceinline__ float box_vote_one(float4 B, float top_c, int a, floa
     bool vote = false;
     if (j < a && cand(j)) vote = iou_bbox(B, box(j)) >= thresh;                   // boxes.py:292
     const uint64_t bal = __ballot(vote);
-    if (vote) vl[m + __builtin_popcountll(bal & ((1ull << lane) - 1ull))] = j;
+    if (vote) vl[m + lanes_below(bal, lane)] = j;
     m += __builtin_popcountll(bal);
   }
   __syncthreads();
@@ -168,9 +169,7 @@ __device__ float vote_score(int method, float beta, VoteScratch& vs, int nw, int
     for (int w0 = 0; w0 < nw; w0 += 64) {
       const int w = w0 + lane;
       const int pc = w < nw ? __builtin_popcountll(vs.w[w]) : 0;
-      int incl = pc;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+      const int incl = wave_incl_scan(pc, lane);
       if (w < nw) vs.pre[w] = carry + incl - pc;
       carry += __shfl(incl, 63, 64);
     }

@@ -25,11 +25,14 @@
 //                    mapping requested the mapping runs after the vote, on the voted boxes (det_fpn_map, one more launch).
 //   Launch count is fixed per option set (graph capture): + det_soft_nms with Soft-NMS, + det_vote (+ det_fpn_map) with voting.
 #include "block_sort.h"
+#include "box_decode.h"
 #include "box_vote.h"
 #include "dtc_common.h"
 #include "fpn_map.h"
+#include "iou_threshold.h"
 #include "radix_select.h"
 #include "soft_nms_walk.h"
+#include "wave_ops.h"
 
 namespace dtc {
 DTC_PT_TABLE(detections)
@@ -67,24 +70,6 @@ struct DetParams {
 };
 
 constexpr int kCandWords = 64;   // bitmap words per segment: R <= 4096
-
-// lib/utils/boxes.py:168-208 for one (roi, class)
-__device__ __forceinline__ void decode_det(const float roi[4], float sf, const float* d, float wx, float wy, float ww,
-                                           float wh, float im_h, float im_w, float out[4]) {
-  const float x1 = fdiv(roi[0], sf), y1 = fdiv(roi[1], sf), x2 = fdiv(roi[2], sf), y2 = fdiv(roi[3], sf);  // result_utils.py:77
-  const float widths = x2 - x1 + 1.0f, heights = y2 - y1 + 1.0f;           // boxes.py:178-179
-  const float ctr_x = x1 + 0.5f * widths, ctr_y = y1 + 0.5f * heights;     // :180-181
-  const float dx = fdiv(d[0], wx), dy = fdiv(d[1], wy);                    // :184-185
-  float dw = fdiv(d[2], ww), dh = fdiv(d[3], wh);                          // :186-187
-  const float clipv = 4.135166556742356f;                                  // :73
-  dw = fminf(dw, clipv); dh = fminf(dh, clipv);                            // :190-191
-  const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;       // :193-194
-  const float pw = fexp_cr(dw) * widths, ph = fexp_cr(dh) * heights;       // :195-196
-  float b0 = pcx - 0.5f * pw, b1 = pcy - 0.5f * ph;                        // :200-202
-  float b2 = pcx + 0.5f * pw - 1.f, b3 = pcy + 0.5f * ph - 1.f;            // :204-206
-  out[0] = fmaxf(fminf(b0, im_w - 1.f), 0.f); out[1] = fmaxf(fminf(b1, im_h - 1.f), 0.f);  // :158-164
-  out[2] = fmaxf(fminf(b2, im_w - 1.f), 0.f); out[3] = fmaxf(fminf(b3, im_h - 1.f), 0.f);
-}
 
 // ---- box-head epilogue fusion: class scores handed over as LOGITS -----------------------------------------
 // The reference applies F.softmax to the cls_score layer's output (lib/model/detector.py:281) and hands the [R,81]
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       base = __builtin_amdgcn_readfirstlane(base);
       if (ok) {
         qs[r] = s;
-        keys[base + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = make_desc_key(s, (uint32_t)r);
+        keys[base + lanes_below(m, lane)] = make_desc_key(s, (uint32_t)r);
       }
     }
     R0 += 4 * kDetThreads;
@@ -185,10 +170,8 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     } else {
       const float* roi = p.rois5 + ((size_t)b * p.R + r) * 5 + 1;
       const float* d = p.bbox_pred + ((size_t)b * p.R + r) * 4 * p.n_cls + 4 * j;
-      const float rr[4] = {roi[0], roi[1], roi[2], roi[3]};
-      float o[4];
-      decode_det(rr, sf, d, p.wx, p.wy, p.ww, p.wh, im_h, im_w, o);
-      v = make_float4(o[0], o[1], o[2], o[3]);
+      const float x1 = fdiv(roi[0], sf), y1 = fdiv(roi[1], sf), x2 = fdiv(roi[2], sf), y2 = fdiv(roi[3], sf);  // result_utils.py:77
+      v = decode_clip<true>(x1, y1, x2, y2, d, p.wx, p.wy, p.ww, p.wh, im_h, im_w);   // the class's box, clipped to the original image
     }
     return v;
   };
@@ -196,15 +179,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     // Soft-NMS input: the candidates in dets_j order (np.where is ascending, :127) -- an ordered compaction of the bitmap: wave 0
     // scans the popcounts of the <= 64 words, each lane lists its word's rois; then every thread decodes
     uint32_t* lst = reinterpret_cast<uint32_t*>(smem);        // over the (unused) sort keys: n * 4 <= np2_max * 8 bytes
-    if (wv == 0) {
-      uint64_t w = lane < nw ? cbits_s[lane] : 0ull;
-      const int pc = __builtin_popcountll(w);
-      int incl = pc;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
-      int k = incl - pc;
-      while (w) { lst[k++] = (uint32_t)(lane * 64 + __builtin_ctzll(w)); w &= w - 1ull; }
-    }
+    if (wv == 0) expand_bitmap(lane < nw ? cbits_s[lane] : 0ull, lane, lst);
     __syncthreads();
     for (int k = tid; k < n; k += kDetThreads) {
       const int r = (int)lst[k];
@@ -231,7 +206,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
   }
   __syncthreads();
   DTC_PT(0, ptb, 3);
-  DTC_PT(0, ptb, 4);
   // ---- the segment's hard NMS, here (cython_nms.pyx:37-87: greedy over the score order; the kept box of rank i suppresses every
   // later box j with inter / (area_i + area_j - inter) >= thresh, IEEE division).  The class segments of a detection batch hold tens
   // of candidates (one 64-row block); as a separate launch pair (mask tiles + reduce over 640 segments) they cost 25 us of which
@@ -253,19 +227,15 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     __syncthreads();
     const float thr = p.nms_thresh;
     const bool thr_pos = thr > 0.f;
-    auto area_of = [](const float4& b) { return (b.z - b.x + 1.f) * (b.w - b.y + 1.f); };           // :44
-    // `inter / (area_r + area_c - inter) >= thresh` with an IEEE division -- decided WITHOUT dividing whenever the sign of
-    // d = fl(inter - fl(thresh * u)) is reliable (|d| > 2^-21 thresh u, u > 0, thresh > 0: rounding is monotone, nms.hip explains);
-    // the division only when some lane of the wavefront is inside that band (about one pair in 10^6)
+    // `inter / (area_r + area_c - inter) >= thresh` with an IEEE division -- decided from the sign of inter - thresh * u; the division
+    // only when some lane of the wavefront is inside the band where that sign is not reliable (iou_threshold.h)
     auto iou_ge = [&](const float4& r, float rarea, const float4& c, float carea) {
       const float xx1 = fmaxf(r.x, c.x), yy1 = fmaxf(r.y, c.y), xx2 = fminf(r.z, c.z), yy2 = fminf(r.w, c.w);   // :76-79
       const float w = fmaxf(0.0f, xx2 - xx1 + 1.f), h = fmaxf(0.0f, yy2 - yy1 + 1.f);                         // :80-81
       const float inter = w * h;                                                                            // :82
       const float u = rarea + carea - inter;
-      const float pu = thr * u;
-      const float d = inter - pu;
-      const float t = __builtin_fabsf(d) - pu * 4.76837158203125e-07f;                                       // 2^-21
-      const bool unsure = !(fminf(t, u) > 0.f);
+      float d;
+      const bool unsure = iou_band(inter, u, thr, d);
       if (__builtin_amdgcn_ballot_w64(unsure) == 0ull && thr_pos) return d > 0.f;
       return (unsure || !thr_pos) ? fdiv(inter, u) >= thr : d > 0.f;                                         // :83-84
     };
@@ -277,11 +247,11 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       const int i0 = rb * 64, nrow = min(64, n - i0);
       // (1) diagonal tile: which rows r < lane of this block suppress column i0 + lane; wave wv tests rows [16 wv, 16 wv + 16)
       const float4 cbx = lane < nrow ? sbox[i0 + lane] : pad;
-      const float carea = area_of(cbx);
+      const float carea = box_area(cbx);
       uint32_t part = 0;
       for (int r = 16 * wv; r < min(16 * wv + 16, nrow); r++) {
         const float4 rbx = sbox[i0 + r];                       // uniform address: LDS broadcast
-        const bool sup = lane > r && lane < nrow && iou_ge(rbx, area_of(rbx), cbx, carea);
+        const bool sup = lane > r && lane < nrow && iou_ge(rbx, box_area(rbx), cbx, carea);
         part |= sup ? (1u << (r - 16 * wv)) : 0u;
       }
       diag_s[wv][lane] = part;
@@ -303,7 +273,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
           keptm = nk;
         }
         const int base = kept_s;
-        if ((keptm >> lane) & 1ull) K[base + __builtin_popcountll(keptm & ((1ull << lane) - 1ull))] = keys[i0 + lane];
+        if ((keptm >> lane) & 1ull) K[base + lanes_below(keptm, lane)] = keys[i0 + lane];
         if (lane == 0) { keptm_s = keptm; kept_s = base + __builtin_popcountll(keptm); }
       }
       __syncthreads();
@@ -317,11 +287,11 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
         for (int c0 = i0 + 64; c0 < n; c0 += 64) {
           const int j = c0 + lane;
           const float4 cj = j < n ? sbox[j] : pad;
-          const float aj = area_of(cj);
+          const float aj = box_area(cj);
           bool sup = false;
           for (uint64_t km = mine_rows; km; km &= km - 1ull) {   // uniform
             const float4 rbx = sbox[i0 + __builtin_ctzll(km)];
-            sup = sup || iou_ge(rbx, area_of(rbx), cj, aj);
+            sup = sup || iou_ge(rbx, box_area(rbx), cj, aj);
           }
           const uint64_t m = __ballot(j < n && sup);
           if (lane == 0 && m) atomicOr(reinterpret_cast<unsigned long long*>(&removed[c0 >> 6]), (unsigned long long)m);
@@ -410,7 +380,7 @@ __global__ __launch_bounds__(kVsThreads) void det_vote_score_kernel(VoteScorePar
   for (int r = tid; r < nr; r += kVsThreads) {
     const uint64_t w = cbits_s[r >> 6];
     if ((w >> (r & 63)) & 1ull) {
-      const int k = wpre_s[r >> 6] + __builtin_popcountll(w & ((1ull << (r & 63)) - 1ull));
+      const int k = wpre_s[r >> 6] + lanes_below(w, r & 63);
       cb[k] = qb[r];
       cs[k] = qs[r];
     }
@@ -443,7 +413,6 @@ struct FinParams {
   const int32_t* keep_count;  // [S]
   const float* q_boxes;       // [S, R, 4]
   const float* q_scores;      // [S, R]  the emitted score of a hard-NMS row (the voted scores with a vote scoring: v_scores)
-  const int32_t* q_roi;       // [S, R]
   const float* scale;         // [B]
   int R, n_cls, max_det, max_out;
   float* dets;                // [B, max_out, 6]
@@ -678,7 +647,7 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
           ok = o >= T;                                                       // :161 `>=`
         }
         const uint64_t bal = __ballot(ok);
-        const int slot = slot0 + __builtin_popcountll(bal & ((1ull << lane) - 1ull));
+        const int slot = slot0 + lanes_below(bal, lane);
         if (ok && slot < p.max_out) emit(slot, c, 0, false, e);
         slot0 += __builtin_popcountll(bal);
       }
@@ -774,185 +743,207 @@ __global__ __launch_bounds__(kMapThreads) void det_fpn_map_kernel(FpnMapOut fm, 
   fpn_map_rows(fm, b, max_out, min(det_count[b], max_out), [&](int t) { return ds[t]; }, code_s, key_s);
 }
 
-static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
-}  // namespace dtc
-
-namespace dtc {
 struct DetPlan { size_t sorted_boxes, q_boxes, q_scores, q_roi, cand_count, kept_key, keep_count, sm_stats, cand_bits, v_scores, total; };
-static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits = false, bool with_vscores = false) {
+static DetPlan det_plan(int batch, int R, int n_cls, bool with_bits, bool with_vscores) {
   DetPlan d;
   const size_t S = (size_t)batch * (n_cls - 1);
-  size_t o = 0;
-  d.sorted_boxes = o; o += al256(S * R * 4 * sizeof(float));
-  d.q_boxes = o; o += al256(S * R * 4 * sizeof(float));
-  d.q_scores = o; o += al256(S * R * sizeof(float));
-  d.q_roi = o; o += al256(S * R * sizeof(int32_t));
-  d.cand_count = o; o += al256(S * sizeof(int32_t));
-  d.kept_key = o; o += al256(S * R * sizeof(uint64_t));
-  d.keep_count = o; o += al256(S * sizeof(int32_t));
-  d.sm_stats = o; o += al256((size_t)batch * R * 2 * sizeof(double));
-  d.cand_bits = o; if (with_bits) o += al256(S * kCandWords * sizeof(uint64_t));
-  d.v_scores = o; if (with_vscores) o += al256(S * R * sizeof(float));
-  d.total = o;
+  Carve w{256};
+  d.sorted_boxes = w.take(S * R * 4 * sizeof(float));
+  d.q_boxes = w.take(S * R * 4 * sizeof(float));
+  d.q_scores = w.take(S * R * sizeof(float));
+  d.q_roi = w.take(S * R * sizeof(int32_t));           // the Soft-NMS path's dets_j order
+  d.cand_count = w.take(S * sizeof(int32_t));
+  d.kept_key = w.take(S * R * sizeof(uint64_t));
+  d.keep_count = w.take(S * sizeof(int32_t));
+  d.sm_stats = w.take((size_t)batch * R * 2 * sizeof(double));
+  d.cand_bits = w.take(with_bits ? S * kCandWords * sizeof(uint64_t) : 0);
+  d.v_scores = w.take(with_vscores ? S * R * sizeof(float) : 0);
+  d.total = w.end;
   return d;
 }
-}  // namespace dtc
 
-DTC_API size_t dtc_postprocess_detections_workspace_bytes(int batch, int max_rois, int n_cls) {
-  if (batch < 1 || max_rois < 1 || n_cls < 2) return 0;
-  return dtc::det_plan(batch, max_rois, n_cls).total;
-}
+// What the options make of a call, decided once for the size entries and the launcher.
+struct DetMode {
+  int soft;       // Soft-NMS walk method (0 hard, 1 linear, 2 gaussian) or -1: the in-workgroup hard NMS
+  bool vote;      // bbox voting of the emitted rows
+  int method;     // the vote's scoring (kVoteID: the score stays)
+  bool scored() const { return method != kVoteID; }
+  bool bits() const { return soft >= 0 || vote; }        // the candidate bitmap is kept
+};
 
-// dtc_det_options validation (host only) -> DTC_OK / DTC_EINVAL; *soft = Soft-NMS walk method (0 hard, 1 linear, 2 gaussian) or -1
-static int det_options_check(const dtc_det_options* opt, int* soft, bool* vote) {
-  *soft = -1; *vote = false;
-  if (!opt) return DTC_OK;
-  if (opt->nms_method < 0 || opt->nms_method > 3) return DTC_EINVAL;
-  if (opt->nms_method == 2 && !(opt->soft_sigma > 0.f)) return DTC_EINVAL;
-  if (opt->bbox_vote != 0 && opt->bbox_vote != 1) return DTC_EINVAL;
-  if (opt->bbox_vote && !(opt->bbox_vote_thresh > 0.f && opt->bbox_vote_thresh <= 1.f)) return DTC_EINVAL;
-  *soft = opt->nms_method == 0 ? -1 : opt->nms_method == 3 ? 0 : opt->nms_method;
-  *vote = opt->bbox_vote != 0;
+// dtc_det_options / dtc_vote_scoring validation (host only) -> DTC_OK / DTC_EINVAL
+static int det_mode(const dtc_det_options* opt, const dtc_vote_scoring* scoring, DetMode* m) {
+  m->soft = -1; m->vote = false; m->method = kVoteID;
+  if (opt) {
+    if (opt->nms_method < 0 || opt->nms_method > 3) return DTC_EINVAL;
+    if (opt->nms_method == 2 && !(opt->soft_sigma > 0.f)) return DTC_EINVAL;
+    if (opt->bbox_vote != 0 && opt->bbox_vote != 1) return DTC_EINVAL;
+    if (opt->bbox_vote && !(opt->bbox_vote_thresh > 0.f && opt->bbox_vote_thresh <= 1.f)) return DTC_EINVAL;
+    m->soft = opt->nms_method == 0 ? -1 : opt->nms_method == 3 ? 0 : opt->nms_method;
+    m->vote = opt->bbox_vote != 0;
+  }
+  if (scoring) {
+    if (scoring->method < kVoteID || scoring->method > kVoteQuasiSum) return DTC_EINVAL;
+    if (!(scoring->beta > 0.f) || !std::isfinite(scoring->beta)) return DTC_EINVAL;
+    if (scoring->method != kVoteID && !(opt && opt->bbox_vote == 1)) return DTC_EINVAL;
+    m->method = scoring->method;
+  }
   return DTC_OK;
 }
 
-// dtc_vote_scoring validation (host only) -> DTC_OK / DTC_EINVAL; *method = the scoring (kVoteID for NULL)
-static int vote_scoring_check(const dtc_det_options* opt, const dtc_vote_scoring* scoring, int* method) {
-  *method = dtc::kVoteID;
-  if (!scoring) return DTC_OK;
-  if (scoring->method < dtc::kVoteID || scoring->method > dtc::kVoteQuasiSum) return DTC_EINVAL;
-  if (!(scoring->beta > 0.f) || !std::isfinite(scoring->beta)) return DTC_EINVAL;
-  if (scoring->method != dtc::kVoteID && !(opt && opt->bbox_vote == 1)) return DTC_EINVAL;
-  *method = scoring->method;
+// The options checked and the workspace laid out, once per call: DTC_EINVAL for bad options, else the mode and the plan (total 0
+// for a shape that has no layout).  The three *_workspace_bytes entries answer with the total, the launcher carves by the offsets.
+static int det_prepare(int batch, int max_rois, int n_cls, const dtc_det_options* opt, const dtc_vote_scoring* scoring, DetMode* mode,
+                       DetPlan* plan) {
+  *plan = DetPlan{};
+  if (det_mode(opt, scoring, mode) != DTC_OK) return DTC_EINVAL;
+  if (batch >= 1 && max_rois >= 1 && n_cls >= 2) *plan = det_plan(batch, max_rois, n_cls, mode->bits(), mode->scored());
   return DTC_OK;
 }
-
-DTC_API size_t dtc_postprocess_detections_ex2_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt,
-                                                              const dtc_vote_scoring* scoring) {
-  int soft, method;
-  bool vote;
-  if (batch < 1 || max_rois < 1 || n_cls < 2 || det_options_check(opt, &soft, &vote) != DTC_OK ||
-      vote_scoring_check(opt, scoring, &method) != DTC_OK)
-    return 0;
-  return dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote, method != dtc::kVoteID).total;
+static size_t det_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt, const dtc_vote_scoring* scoring) {
+  DetMode mode;
+  DetPlan pl;
+  return det_prepare(batch, max_rois, n_cls, opt, scoring, &mode, &pl) == DTC_OK ? pl.total : 0;
 }
 
-DTC_API size_t dtc_postprocess_detections_ex_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt) {
-  int soft;
-  bool vote;
-  if (batch < 1 || max_rois < 1 || n_cls < 2 || det_options_check(opt, &soft, &vote) != DTC_OK) return 0;
-  return dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote).total;
-}
+// One call of the batched detection post-processing, whichever entry it came through; the entries fill it by name.
+struct DetCall {
+  // inputs: rois5 [B, R, 5], n_rois [B] or NULL, cls_score [B, R, n_cls] (probabilities, or logits), bbox_pred [B, R, 4 n_cls];
+  // decoded_boxes [B, R, 4 n_cls] stands in for rois5 / bbox_pred / scaling_factor [B] / im_size [B, 2]
+  const float *rois5 = nullptr, *cls_score = nullptr, *bbox_pred = nullptr, *decoded_boxes = nullptr, *scaling_factor = nullptr,
+              *im_size = nullptr;
+  const int32_t* n_rois = nullptr;
+  bool scores_are_logits = false;
+  int batch = 0, max_rois = 0, n_cls = 0;                                                       // shape
+  float wx = 1.f, wy = 1.f, ww = 1.f, wh = 1.f, score_thresh = 0.f, nms_thresh = 0.f;           // thresholds
+  int max_det = 0;
+  const dtc_det_options* opt = nullptr;                                                         // options, scoring
+  const dtc_vote_scoring* scoring = nullptr;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+  float *dets = nullptr, *det_rois_scaled = nullptr;                                            // outputs
+  int32_t *det_roi = nullptr, *det_count = nullptr;
+  int max_out = 0;
+  const dtc_fpn_map_out* fpn = nullptr;
+  dtc_stream_t stream = nullptr;
+};
 
-static int postprocess_detections_impl(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
-                                       const float* bbox_pred, const float* decoded_boxes, const float* scaling_factor, const float* im_size,
-                                       int batch, int max_rois, int n_cls, float wx, float wy, float ww, float wh,
-                                       float score_thresh, float nms_thresh, int max_det, void* workspace,
-                                       size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
-                                       int32_t* det_count, int max_out, dtc_stream_t stream, const dtc_fpn_map_out* fpn = nullptr,
-                                       const dtc_det_options* opt = nullptr, const dtc_vote_scoring* scoring = nullptr) {
-  int soft, method;
-  bool vote;
-  if (det_options_check(opt, &soft, &vote) != DTC_OK) return DTC_EINVAL;
-  if (vote_scoring_check(opt, scoring, &method) != DTC_OK) return DTC_EINVAL;
-  const bool scored = method != dtc::kVoteID;
-  if (batch < 0 || max_rois < 1 || n_cls < 2 || n_cls - 1 > dtc::kFinMaxCls || max_out < 1) return DTC_EINVAL;
+static int postprocess_detections(const DetCall& c) {
+  const int batch = c.batch, max_rois = c.max_rois, n_cls = c.n_cls, max_out = c.max_out;
+  const dtc_fpn_map_out* fpn = c.fpn;
+  DetMode mode;
+  DetPlan pl;
+  if (det_prepare(batch, max_rois, n_cls, c.opt, c.scoring, &mode, &pl) != DTC_OK) return DTC_EINVAL;
+  if (batch < 0 || max_rois < 1 || n_cls < 2 || n_cls - 1 > kFinMaxCls || max_out < 1) return DTC_EINVAL;
   if (fpn) {
-    if (!det_rois_scaled || !fpn->rois5 || !fpn->roi_levels || !fpn->n_out || !fpn->rois_by_level || !fpn->level_counts || !fpn->idx_restore ||
-        fpn->k_max < fpn->k_min || fpn->k_max - fpn->k_min + 1 > 8)
+    if (!c.det_rois_scaled || !fpn->rois5 || !fpn->roi_levels || !fpn->n_out || !fpn->rois_by_level || !fpn->level_counts ||
+        !fpn->idx_restore || fpn->k_max < fpn->k_min || fpn->k_max - fpn->k_min + 1 > 8)
       return DTC_EINVAL;
-    if (max_out > dtc::kFpnMapMaxRows) return DTC_EUNSUPPORTED;      // longer lists: dtc_fpn_collect_distribute on det_rois_scaled
+    if (max_out > kFpnMapMaxRows) return DTC_EUNSUPPORTED;      // longer lists: dtc_fpn_collect_distribute on det_rois_scaled
   }
   if (batch == 0) return DTC_OK;
   if (max_rois > 4096) return DTC_EUNSUPPORTED;
-  if (!cls_score || !workspace || !dets || !det_roi || !det_count) return DTC_EINVAL;
-  if (!decoded_boxes && (!rois5 || !bbox_pred || !scaling_factor || !im_size)) return DTC_EINVAL;
-  if (decoded_boxes && det_rois_scaled) return DTC_EINVAL;
-  const dtc::DetPlan pl = dtc::det_plan(batch, max_rois, n_cls, soft >= 0 || vote, scored);
-  if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
-  unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dtc::DetParams p;
-  p.rois5 = rois5; p.n_rois = n_rois; p.cls_score = cls_score; p.bbox_pred = bbox_pred; p.scale = scaling_factor;
-  p.decoded = decoded_boxes;
+  if (!c.cls_score || !c.workspace || !c.dets || !c.det_roi || !c.det_count) return DTC_EINVAL;
+  if (!c.decoded_boxes && (!c.rois5 || !c.bbox_pred || !c.scaling_factor || !c.im_size)) return DTC_EINVAL;
+  if (c.decoded_boxes && c.det_rois_scaled) return DTC_EINVAL;
+  if (c.workspace_bytes < pl.total) return DTC_EWORKSPACE;
+  const bool soft = mode.soft >= 0, vote = mode.vote, scored = mode.scored();
+  unsigned char* w = reinterpret_cast<unsigned char*>(c.workspace);
+  hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
+  DetParams p;
+  p.rois5 = c.rois5; p.n_rois = c.n_rois; p.cls_score = c.cls_score; p.bbox_pred = c.bbox_pred; p.scale = c.scaling_factor;
+  p.decoded = c.decoded_boxes;
   p.sm_stats = nullptr;
-  if (scores_are_logits) {
+  if (c.scores_are_logits) {
     double* st = reinterpret_cast<double*>(w + pl.sm_stats);
     const int rows = batch * max_rois;
-    hipLaunchKernelGGL(dtc::det_softmax_stats_kernel, dim3((rows + dtc::kDetThreads / 64 - 1) / (dtc::kDetThreads / 64)),
-                       dim3(dtc::kDetThreads), 0, s, cls_score, rows, n_cls, st);
+    hipLaunchKernelGGL(det_softmax_stats_kernel, dim3((rows + kDetThreads / 64 - 1) / (kDetThreads / 64)), dim3(kDetThreads), 0, s,
+                       c.cls_score, rows, n_cls, st);
     DTC_CHECK_LAUNCH();
     p.sm_stats = st;
   }
-  p.im_size = im_size; p.R = max_rois; p.n_cls = n_cls; p.wx = wx; p.wy = wy; p.ww = ww; p.wh = wh;
-  p.score_thresh = score_thresh;
+  p.im_size = c.im_size; p.R = max_rois; p.n_cls = n_cls; p.wx = c.wx; p.wy = c.wy; p.ww = c.ww; p.wh = c.wh;
+  p.score_thresh = c.score_thresh;
   p.sorted_boxes = reinterpret_cast<float*>(w + pl.sorted_boxes);
   p.q_boxes = reinterpret_cast<float*>(w + pl.q_boxes); p.q_scores = reinterpret_cast<float*>(w + pl.q_scores);
   p.q_roi = reinterpret_cast<int32_t*>(w + pl.q_roi); p.cand_count = reinterpret_cast<int32_t*>(w + pl.cand_count);
   // dynamic LDS: sort keys [next_pow2(R)] x 8 B, then up to kNmsLdsCap boxes in score order (16 B) and one removed-bit per candidate
-  const int np2 = dtc::next_pow2(max_rois);
-  const size_t smem = (size_t)np2 * sizeof(uint64_t) + (size_t)dtc::kNmsLdsCap * sizeof(float4) +
-                      (size_t)((max_rois + 63) / 64) * sizeof(uint64_t);
-  if (smem > 48 * 1024 && dtc::raise_lds_once<dtc::det_candidates_kernel>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
-  uint64_t* kept_key = reinterpret_cast<uint64_t*>(w + pl.kept_key);
-  int32_t* keep_count = reinterpret_cast<int32_t*>(w + pl.keep_count);
-  p.kept_key = kept_key; p.keep_count = keep_count; p.nms_thresh = nms_thresh; p.np2_max = np2;
-  p.soft = soft >= 0 ? 1 : 0;
-  p.cand_bits = soft >= 0 || vote ? reinterpret_cast<uint64_t*>(w + pl.cand_bits) : nullptr;
-  hipLaunchKernelGGL(dtc::det_candidates_kernel, dim3(n_cls - 1, batch), dim3(dtc::kDetThreads), smem, s, p);
+  const int np2 = next_pow2(max_rois);
+  const size_t smem = (size_t)np2 * sizeof(uint64_t) + (size_t)kNmsLdsCap * sizeof(float4) + (size_t)((max_rois + 63) / 64) * sizeof(uint64_t);
+  if (smem > 48 * 1024 && raise_lds_once<det_candidates_kernel>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  p.kept_key = reinterpret_cast<uint64_t*>(w + pl.kept_key);
+  p.keep_count = reinterpret_cast<int32_t*>(w + pl.keep_count);
+  p.nms_thresh = c.nms_thresh; p.np2_max = np2;
+  p.soft = soft ? 1 : 0;
+  p.cand_bits = mode.bits() ? reinterpret_cast<uint64_t*>(w + pl.cand_bits) : nullptr;
+  hipLaunchKernelGGL(det_candidates_kernel, dim3(n_cls - 1, batch), dim3(kDetThreads), smem, s, p);
   DTC_CHECK_LAUNCH();
-  if (soft >= 0) {
-    if (dtc::raise_lds_once<dtc::det_soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
-    hipLaunchKernelGGL(dtc::det_soft_nms_kernel, dim3(n_cls - 1, batch), dim3(64), dtc::soft_nms_lds_bytes(max_rois), s, p,
-                       opt->soft_sigma, nms_thresh, opt->soft_score_thresh, soft);
+  if (soft) {
+    if (raise_lds_once<det_soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+    hipLaunchKernelGGL(det_soft_nms_kernel, dim3(n_cls - 1, batch), dim3(64), soft_nms_lds_bytes(max_rois), s, p, c.opt->soft_sigma,
+                       c.nms_thresh, c.opt->soft_score_thresh, mode.soft);
     DTC_CHECK_LAUNCH();
   }
   float* v_scores = scored ? reinterpret_cast<float*>(w + pl.v_scores) : nullptr;
   if (scored) {
-    dtc::VoteScoreParams vp;
-    vp.n_rois = n_rois; vp.cand_bits = p.cand_bits; vp.q_boxes = p.q_boxes; vp.q_scores = p.q_scores; vp.keep_count = keep_count;
-    vp.kept_key = kept_key; vp.v_scores = v_scores; vp.R = max_rois; vp.n_cls = n_cls; vp.method = method;
-    vp.thresh = opt->bbox_vote_thresh; vp.beta = scoring->beta;
+    VoteScoreParams vp;
+    vp.n_rois = c.n_rois; vp.cand_bits = p.cand_bits; vp.q_boxes = p.q_boxes; vp.q_scores = p.q_scores; vp.keep_count = p.keep_count;
+    vp.kept_key = p.kept_key; vp.v_scores = v_scores; vp.R = max_rois; vp.n_cls = n_cls; vp.method = mode.method;
+    vp.thresh = c.opt->bbox_vote_thresh; vp.beta = c.scoring->beta;
     const size_t vsm = (size_t)max_rois * (sizeof(float4) + sizeof(float));
-    if (vsm > 48 * 1024 && dtc::raise_lds_once<dtc::det_vote_score_kernel>(4096 * (sizeof(float4) + sizeof(float))) != DTC_OK) return DTC_ELAUNCH;
-    hipLaunchKernelGGL(dtc::det_vote_score_kernel, dim3(n_cls - 1, batch), dim3(dtc::kVsThreads), vsm, s, vp);
+    if (vsm > 48 * 1024 && raise_lds_once<det_vote_score_kernel>(4096 * (sizeof(float4) + sizeof(float))) != DTC_OK) return DTC_ELAUNCH;
+    hipLaunchKernelGGL(det_vote_score_kernel, dim3(n_cls - 1, batch), dim3(kVsThreads), vsm, s, vp);
     DTC_CHECK_LAUNCH();
   }
-  dtc::FinParams f;
-  f.kept_key = kept_key; f.keep_count = keep_count; f.q_boxes = p.q_boxes; f.q_scores = scored ? v_scores : p.q_scores;
-  f.q_roi = p.q_roi; f.scale = scaling_factor; f.R = max_rois; f.n_cls = n_cls; f.max_det = max_det; f.max_out = max_out;
-  f.dets = dets; f.det_roi = det_roi; f.det_rois_scaled = det_rois_scaled; f.det_count = det_count;
+  FinParams f;
+  f.kept_key = p.kept_key; f.keep_count = p.keep_count; f.q_boxes = p.q_boxes; f.q_scores = scored ? v_scores : p.q_scores;
+  f.scale = c.scaling_factor; f.R = max_rois; f.n_cls = n_cls; f.max_det = c.max_det; f.max_out = max_out;
+  f.dets = c.dets; f.det_roi = c.det_roi; f.det_rois_scaled = c.det_rois_scaled; f.det_count = c.det_count;
   f.fm.on = fpn && !vote ? 1 : 0;            // with voting the mapping follows the vote (det_fpn_map)
-  f.soft = soft >= 0 ? 1 : 0;
+  f.soft = soft ? 1 : 0;
   if (fpn) {
     f.fm.rois5 = fpn->rois5; f.fm.roi_levels = fpn->roi_levels; f.fm.n_out = fpn->n_out; f.fm.rois_by_level = fpn->rois_by_level;
     f.fm.level_counts = fpn->level_counts; f.fm.idx_restore = fpn->idx_restore; f.fm.roi_order = fpn->roi_order;
     f.fm.roi_desc = fpn->roi_order ? fpn->roi_desc : nullptr; f.fm.k_min = fpn->k_min; f.fm.k_max = fpn->k_max;
-    f.fm.band_log2 = 4;                                               // as dtc_fpn_collect_distribute (fpn.hip)
+    f.fm.band_log2 = kFpnBandLog2;
   }
   long long cap = (long long)max_rois * (n_cls - 1);            // every candidate of every class kept
-  if (cap > dtc::kFinStageMax) cap = dtc::kFinStageMax;
+  if (cap > kFinStageMax) cap = kFinStageMax;
   const int stage_cap = (int)((cap + 3) & ~3ll);
   const size_t fsm = (size_t)stage_cap * 8;
-  if (fsm > 16 * 1024 && dtc::raise_lds_once<dtc::det_finalize_kernel>(116 * 1024) != DTC_OK) return DTC_ELAUNCH;      // + ~37 KB static: under the 160 KB of a CU
-  hipLaunchKernelGGL(dtc::det_finalize_kernel, dim3(batch), dim3(dtc::kFinThreads), fsm, s, f, stage_cap);
+  if (fsm > 16 * 1024 && raise_lds_once<det_finalize_kernel>(116 * 1024) != DTC_OK) return DTC_ELAUNCH;      // + ~37 KB static: under the 160 KB of a CU
+  hipLaunchKernelGGL(det_finalize_kernel, dim3(batch), dim3(kFinThreads), fsm, s, f, stage_cap);
   DTC_CHECK_LAUNCH();
   if (vote) {
-    dtc::VoteParams v;
-    v.n_rois = n_rois; v.cand_bits = p.cand_bits; v.q_boxes = p.q_boxes; v.q_scores = p.q_scores;
-    v.scale = decoded_boxes ? nullptr : scaling_factor; v.det_count = det_count; v.dets = dets; v.det_rois_scaled = det_rois_scaled;
-    v.R = max_rois; v.n_cls = n_cls; v.max_out = max_out; v.thresh = opt->bbox_vote_thresh;
-    hipLaunchKernelGGL(dtc::det_vote_kernel, dim3(max_out, batch), dim3(64), 0, s, v);
+    VoteParams v;
+    v.n_rois = c.n_rois; v.cand_bits = p.cand_bits; v.q_boxes = p.q_boxes; v.q_scores = p.q_scores;
+    v.scale = c.decoded_boxes ? nullptr : c.scaling_factor; v.det_count = c.det_count; v.dets = c.dets; v.det_rois_scaled = c.det_rois_scaled;
+    v.R = max_rois; v.n_cls = n_cls; v.max_out = max_out; v.thresh = c.opt->bbox_vote_thresh;
+    hipLaunchKernelGGL(det_vote_kernel, dim3(max_out, batch), dim3(64), 0, s, v);
     DTC_CHECK_LAUNCH();
     if (fpn) {
-      dtc::FpnMapOut fm = f.fm;
+      FpnMapOut fm = f.fm;
       fm.on = 1;
-      hipLaunchKernelGGL(dtc::det_fpn_map_kernel, dim3(batch), dim3(dtc::kMapThreads), 0, s, fm, det_rois_scaled, det_count, max_out);
+      hipLaunchKernelGGL(det_fpn_map_kernel, dim3(batch), dim3(kMapThreads), 0, s, fm, c.det_rois_scaled, c.det_count, max_out);
       DTC_CHECK_LAUNCH();
     }
   }
   return DTC_OK;
+}
+
+}  // namespace dtc
+
+DTC_API size_t dtc_postprocess_detections_workspace_bytes(int batch, int max_rois, int n_cls) {
+  return dtc::det_workspace_bytes(batch, max_rois, n_cls, nullptr, nullptr);
+}
+
+DTC_API size_t dtc_postprocess_detections_ex_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt) {
+  return dtc::det_workspace_bytes(batch, max_rois, n_cls, opt, nullptr);
+}
+
+DTC_API size_t dtc_postprocess_detections_ex2_workspace_bytes(int batch, int max_rois, int n_cls, const dtc_det_options* opt,
+                                                              const dtc_vote_scoring* scoring) {
+  return dtc::det_workspace_bytes(batch, max_rois, n_cls, opt, scoring);
 }
 
 DTC_API int dtc_postprocess_detections(const float* rois5, const int32_t* n_rois, const float* cls_score,
@@ -961,9 +952,15 @@ DTC_API int dtc_postprocess_detections(const float* rois5, const int32_t* n_rois
                                        float score_thresh, float nms_thresh, int max_det, void* workspace,
                                        size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
                                        int32_t* det_count, int max_out, dtc_stream_t stream) {
-  return postprocess_detections_impl(rois5, n_rois, cls_score, 0, bbox_pred, nullptr, scaling_factor, im_size, batch, max_rois, n_cls, wx,
-                                     wy, ww, wh, score_thresh, nms_thresh, max_det, workspace, workspace_bytes, dets, det_roi,
-                                     det_rois_scaled, det_count, max_out, stream);
+  dtc::DetCall c;
+  c.rois5 = rois5; c.bbox_pred = bbox_pred; c.scaling_factor = scaling_factor; c.im_size = im_size;
+  c.wx = wx; c.wy = wy; c.ww = ww; c.wh = wh; c.det_rois_scaled = det_rois_scaled;
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = cls_score;
+  return dtc::postprocess_detections(c);
 }
 
 DTC_API int dtc_postprocess_detections_logits(const float* rois5, const int32_t* n_rois, const float* cls_logits,
@@ -972,9 +969,15 @@ DTC_API int dtc_postprocess_detections_logits(const float* rois5, const int32_t*
                                               float score_thresh, float nms_thresh, int max_det, void* workspace,
                                               size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
                                               int32_t* det_count, int max_out, dtc_stream_t stream) {
-  return postprocess_detections_impl(rois5, n_rois, cls_logits, 1, bbox_pred, nullptr, scaling_factor, im_size, batch, max_rois, n_cls, wx,
-                                     wy, ww, wh, score_thresh, nms_thresh, max_det, workspace, workspace_bytes, dets, det_roi,
-                                     det_rois_scaled, det_count, max_out, stream);
+  dtc::DetCall c;
+  c.rois5 = rois5; c.bbox_pred = bbox_pred; c.scaling_factor = scaling_factor; c.im_size = im_size;
+  c.wx = wx; c.wy = wy; c.ww = ww; c.wh = wh; c.det_rois_scaled = det_rois_scaled;
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = cls_logits; c.scores_are_logits = true;
+  return dtc::postprocess_detections(c);
 }
 
 DTC_API int dtc_postprocess_detections_fpn(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
@@ -984,9 +987,15 @@ DTC_API int dtc_postprocess_detections_fpn(const float* rois5, const int32_t* n_
                                            size_t workspace_bytes, float* dets, int32_t* det_roi, float* det_rois_scaled,
                                            int32_t* det_count, int max_out, const dtc_fpn_map_out* fpn, dtc_stream_t stream) {
   if (!fpn) return DTC_EINVAL;
-  return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, nullptr, scaling_factor, im_size, batch,
-                                     max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace, workspace_bytes, dets,
-                                     det_roi, det_rois_scaled, det_count, max_out, stream, fpn);
+  dtc::DetCall c;
+  c.rois5 = rois5; c.bbox_pred = bbox_pred; c.scaling_factor = scaling_factor; c.im_size = im_size;
+  c.wx = wx; c.wy = wy; c.ww = ww; c.wh = wh; c.det_rois_scaled = det_rois_scaled;
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = cls_score; c.scores_are_logits = scores_are_logits != 0; c.fpn = fpn;
+  return dtc::postprocess_detections(c);
 }
 
 DTC_API int dtc_box_results_nms_limit(const float* scores, const float* boxes, const int32_t* n_rois, int batch, int max_rois,
@@ -994,9 +1003,13 @@ DTC_API int dtc_box_results_nms_limit(const float* scores, const float* boxes, c
                                       size_t workspace_bytes, float* dets, int32_t* det_roi, int32_t* det_count, int max_out,
                                       dtc_stream_t stream) {
   if (!boxes) return DTC_EINVAL;
-  return postprocess_detections_impl(nullptr, n_rois, scores, 0, nullptr, boxes, nullptr, nullptr, batch, max_rois, n_cls, 1.f, 1.f,
-                                     1.f, 1.f, score_thresh, nms_thresh, max_det, workspace, workspace_bytes, dets, det_roi,
-                                     nullptr, det_count, max_out, stream);
+  dtc::DetCall c;                                  // no decode: the weights stay 1, there is no scale and no det_rois_scaled
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = scores; c.decoded_boxes = boxes;
+  return dtc::postprocess_detections(c);
 }
 
 DTC_API int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
@@ -1007,9 +1020,15 @@ DTC_API int dtc_postprocess_detections_ex(const float* rois5, const int32_t* n_r
                                           float* det_rois_scaled, int32_t* det_count, int max_out, const dtc_fpn_map_out* fpn,
                                           dtc_stream_t stream) {
   if (decoded_boxes && fpn) return DTC_EINVAL;           // the mapping reads det_rois_scaled, which the decoded-boxes form has not
-  return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, decoded_boxes, scaling_factor,
-                                     im_size, batch, max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace,
-                                     workspace_bytes, dets, det_roi, det_rois_scaled, det_count, max_out, stream, fpn, opt);
+  dtc::DetCall c;
+  c.rois5 = rois5; c.bbox_pred = bbox_pred; c.scaling_factor = scaling_factor; c.im_size = im_size;
+  c.wx = wx; c.wy = wy; c.ww = ww; c.wh = wh; c.det_rois_scaled = det_rois_scaled;
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = cls_score; c.scores_are_logits = scores_are_logits != 0; c.decoded_boxes = decoded_boxes; c.opt = opt; c.fpn = fpn;
+  return dtc::postprocess_detections(c);
 }
 
 DTC_API int dtc_postprocess_detections_ex2(const float* rois5, const int32_t* n_rois, const float* cls_score, int scores_are_logits,
@@ -1020,7 +1039,14 @@ DTC_API int dtc_postprocess_detections_ex2(const float* rois5, const int32_t* n_
                                            int32_t* det_roi, float* det_rois_scaled, int32_t* det_count, int max_out,
                                            const dtc_fpn_map_out* fpn, dtc_stream_t stream) {
   if (decoded_boxes && fpn) return DTC_EINVAL;
-  return postprocess_detections_impl(rois5, n_rois, cls_score, scores_are_logits ? 1 : 0, bbox_pred, decoded_boxes, scaling_factor,
-                                     im_size, batch, max_rois, n_cls, wx, wy, ww, wh, score_thresh, nms_thresh, max_det, workspace,
-                                     workspace_bytes, dets, det_roi, det_rois_scaled, det_count, max_out, stream, fpn, opt, scoring);
+  dtc::DetCall c;
+  c.rois5 = rois5; c.bbox_pred = bbox_pred; c.scaling_factor = scaling_factor; c.im_size = im_size;
+  c.wx = wx; c.wy = wy; c.ww = ww; c.wh = wh; c.det_rois_scaled = det_rois_scaled;
+  c.n_rois = n_rois; c.batch = batch; c.max_rois = max_rois; c.n_cls = n_cls;
+  c.score_thresh = score_thresh; c.nms_thresh = nms_thresh; c.max_det = max_det;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.dets = dets; c.det_roi = det_roi; c.det_count = det_count; c.max_out = max_out; c.stream = stream;
+  c.cls_score = cls_score; c.scores_are_logits = scores_are_logits != 0; c.decoded_boxes = decoded_boxes; c.opt = opt;
+  c.scoring = scoring; c.fpn = fpn;
+  return dtc::postprocess_detections(c);
 }

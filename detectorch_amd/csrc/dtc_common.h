@@ -99,6 +99,14 @@ __device__ __forceinline__ void store_stream8(void* d, uint32_t x, uint32_t y) {
 }
 
 __host__ __device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
+__host__ __device__ __forceinline__ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// A workspace layout, carved front to back: take(bytes) = the offset of the next block, every block rounded up to `align`
+// (detections, nms, proposals: 256; proposal_prep: 16).  The *_workspace_bytes entry answers with `end`, the launcher uses the
+// offsets: one text for the size and the carve.
+struct Carve {
+  size_t align, end = 0;
+  size_t take(size_t bytes) { const size_t at = end; end += align_up(bytes, align); return at; }
+};
 
 // Development aid (-DDTC_PHASE_TRACE, tools/r02b/phase_trace.py): thread 0 of the first workgroups of an instrumented kernel
 // stamps the 100 MHz wall clock at its phase boundaries into a per-file table [kernel id][workgroup][mark] that

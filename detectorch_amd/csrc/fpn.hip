@@ -9,9 +9,11 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "dtc_common.h"
 #include "fpn_map.h"
+#include "wave_ops.h"
 
 namespace dtc {
 DTC_PT_TABLE(fpn)
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_distribute_kernel(Fpn
     for (int l = 0; l < nl_out; l++) {
       const uint64_t mk = __ballot(lvl == l);
       if (lane == 0) wave_cnt[l][wv] = __builtin_popcountll(mk);
-      if (lvl == l) my_before = __builtin_popcountll(mk & ((1ull << lane) - 1ull));
+      if (lvl == l) my_before = lanes_below(mk, lane);
     }
     __syncthreads();
     int pos_in_level = -1;
@@ -401,7 +403,7 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
     for (int l = 0; l < nl_out; l++) {                                         // np.where(lvls == lvl)[0] is ascending (:123)
       const uint64_t mk = __ballot(lvl[rr] == l);
       if (lane == 0) wave_cnt[l][rr * kRW + wv] = __builtin_popcountll(mk);
-      if (lvl[rr] == l) my_before[rr] = __builtin_popcountll(mk & ((1ull << lane) - 1ull));
+      if (lvl[rr] == l) my_before[rr] = lanes_below(mk, lane);
     }
     // order key for the RoIAlign visiting order (see the general kernel): level | band | x, all in feature pixels
     const int r = rr * kFpnThreads + tid;
@@ -461,9 +463,7 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
   __syncthreads();
   uint32_t hv = 0, incl = 0;
   if (tid < kOrderBuckets) {
-    hv = bstart[tid]; incl = hv;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    hv = bstart[tid]; incl = wave_incl_scan(hv, lane);
     if (lane == 63) bwsum[wv] = incl;
   }
   __syncthreads();
@@ -505,6 +505,7 @@ static int fpn_collect_launch(dtc::FpnParams p, int batch, long long n_max, dtc_
   const int n_in_levels = p.L_in, post_nms_top_n = p.top_n, in_stride = p.P;
   const float* in_scores = p.in_scores;
   const int inputs_sorted = p.inputs_sorted;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   size_t smem = in_scores ? (size_t)dtc::next_pow2((int)n_max) * sizeof(uint64_t) : 16;
   if (in_scores && inputs_sorted) smem = (size_t)post_nms_top_n * sizeof(uint64_t) + (size_t)n_max * sizeof(float) + 16;
   if (p.roi_order) { const size_t so = (size_t)(dtc::next_pow2(post_nms_top_n) < 4 ? 4 : dtc::next_pow2(post_nms_top_n)) * sizeof(uint64_t) * 2; if (so > smem) smem = so; }
@@ -520,25 +521,35 @@ static int fpn_collect_launch(dtc::FpnParams p, int batch, long long n_max, dtc_
                        (size_t)(in_scores && n_in_levels > 1 ? n_max + (long long)(n_in_levels - 1) * post_nms_top_n : 0) * 8 +
                        (p.keep ? (size_t)n_max * 4 : 0) + 16;
     if (fsm <= 150 * 1024) {
-      if (R == 1) {
-        if (dtc::raise_lds_once<dtc::fpn_collect_fast_kernel<1>>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
-        hipLaunchKernelGGL(dtc::fpn_collect_fast_kernel<1>, dim3(batch), dim3(dtc::kFpnThreads), fsm, reinterpret_cast<hipStream_t>(stream), p, (int)n_max);
-      } else {
-        if (dtc::raise_lds_once<dtc::fpn_collect_fast_kernel<2>>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
-        hipLaunchKernelGGL(dtc::fpn_collect_fast_kernel<2>, dim3(batch), dim3(dtc::kFpnThreads), fsm, reinterpret_cast<hipStream_t>(stream), p, (int)n_max);
-      }
-      DTC_CHECK_LAUNCH();
-      return DTC_OK;
+      auto run = [&](auto r_tag) -> int {
+        constexpr int kR = decltype(r_tag)::value;
+        if (dtc::raise_lds_once<dtc::fpn_collect_fast_kernel<kR>>(152 * 1024) != DTC_OK) return DTC_ELAUNCH;
+        hipLaunchKernelGGL(dtc::fpn_collect_fast_kernel<kR>, dim3(batch), dim3(dtc::kFpnThreads), fsm, s, p, (int)n_max);
+        DTC_CHECK_LAUNCH();
+        return DTC_OK;
+      };
+      return R == 1 ? run(std::integral_constant<int, 1>{}) : run(std::integral_constant<int, 2>{});
     }
   }
   if (p.keep) return DTC_EUNSUPPORTED;         // the keep form exists in the fast kernel only: dtc_gather_kept + dtc_fpn_collect_distribute
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
     if (dtc::raise_lds_once<dtc::fpn_collect_distribute_kernel>(144 * 1024) != DTC_OK) return DTC_ELAUNCH;
   }
-  hipLaunchKernelGGL(dtc::fpn_collect_distribute_kernel, dim3(batch), dim3(dtc::kFpnThreads), smem,
-                     reinterpret_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(dtc::fpn_collect_distribute_kernel, dim3(batch), dim3(dtc::kFpnThreads), smem, s, p);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
+}
+
+// The kernels' parameter block, everything the two entries share: the outputs, the level range and the visiting-order band.  The
+// entries name their inputs themselves.
+static dtc::FpnParams fpn_params(int post_nms_top_n, int k_min, int k_max, float* rois5, float* roi_scores, int32_t* roi_levels,
+                                 int32_t* n_out, float* rois_by_level, int32_t* level_counts, int32_t* idx_restore, int32_t* roi_order,
+                                 float* roi_desc) {
+  dtc::FpnParams p = {};
+  p.top_n = post_nms_top_n; p.k_min = k_min; p.k_max = k_max; p.band_log2 = dtc::kFpnBandLog2;
+  p.rois5 = rois5; p.roi_scores = roi_scores; p.roi_levels = roi_levels; p.n_out = n_out; p.rois_by_level = rois_by_level;
+  p.level_counts = level_counts; p.idx_restore = idx_restore; p.roi_order = roi_order; p.roi_desc = roi_order ? roi_desc : nullptr;
+  return p;
 }
 
 DTC_API int dtc_fpn_collect_distribute(const float* in_boxes, const float* in_scores, const int32_t* in_counts, int batch,
@@ -554,15 +565,10 @@ DTC_API int dtc_fpn_collect_distribute(const float* in_boxes, const float* in_sc
     return DTC_EINVAL;
   const long long n_max = (long long)n_in_levels * in_stride;
   if (in_scores && n_max > 16384) return DTC_EUNSUPPORTED;
-  dtc::FpnParams p;
+  dtc::FpnParams p = fpn_params(post_nms_top_n, k_min, k_max, rois5, roi_scores, roi_levels, n_out, rois_by_level, level_counts,
+                                idx_restore, roi_order, roi_desc);
   p.in_boxes = in_boxes; p.in_scores = in_scores; p.in_counts = in_counts; p.L_in = n_in_levels; p.P = in_stride;
-  p.top_n = post_nms_top_n; p.k_min = k_min; p.k_max = k_max; p.inputs_sorted = inputs_sorted; p.rois5 = rois5; p.roi_scores = roi_scores;
-  p.roi_levels = roi_levels; p.n_out = n_out; p.rois_by_level = rois_by_level; p.level_counts = level_counts;
-  p.keep = nullptr; p.k_stride = 0;
-  // visiting-order band height (log2 feature rows): 16 rows suits the cluster-stationary RoIAlign kernel (clusters of ~5
-  // neighbours stay ~28 rows x 32 pixels; measured 8 rows 0.48, 16 rows 0.41, 32 rows 0.43 ms per 8000-RoI box-head launch)
-  p.band_log2 = 4;
-  p.idx_restore = idx_restore; p.roi_order = roi_order; p.roi_desc = roi_order ? roi_desc : nullptr;
+  p.inputs_sorted = inputs_sorted;                       // keep = NULL, k_stride = 0: the lists are read in place
   return fpn_collect_launch(p, batch, n_max, stream);
 }
 
@@ -578,12 +584,9 @@ DTC_API int dtc_fpn_collect_distribute_kept(const float* sorted_boxes, const flo
   if (!sorted_boxes || !sorted_scores || !keep || !keep_count || !rois5 || !roi_levels || !n_out || !rois_by_level || !level_counts ||
       !idx_restore)
     return DTC_EINVAL;
-  const long long n_max = (long long)n_in_levels * keep_stride;
-  dtc::FpnParams p;
+  dtc::FpnParams p = fpn_params(post_nms_top_n, k_min, k_max, rois5, roi_scores, roi_levels, n_out, rois_by_level, level_counts,
+                                idx_restore, roi_order, roi_desc);
   p.in_boxes = sorted_boxes; p.in_scores = sorted_scores; p.in_counts = keep_count; p.L_in = n_in_levels; p.P = keep_stride;
-  p.top_n = post_nms_top_n; p.k_min = k_min; p.k_max = k_max; p.inputs_sorted = 1; p.rois5 = rois5; p.roi_scores = roi_scores;
-  p.roi_levels = roi_levels; p.n_out = n_out; p.rois_by_level = rois_by_level; p.level_counts = level_counts;
-  p.keep = keep; p.k_stride = k_stride; p.band_log2 = 4;
-  p.idx_restore = idx_restore; p.roi_order = roi_order; p.roi_desc = roi_order ? roi_desc : nullptr;
-  return fpn_collect_launch(p, batch, n_max, stream);
+  p.inputs_sorted = 1; p.keep = keep; p.k_stride = k_stride;
+  return fpn_collect_launch(p, batch, (long long)n_in_levels * keep_stride, stream);
 }

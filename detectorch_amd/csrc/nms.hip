@@ -20,7 +20,9 @@
 
 #include "block_sort.h"
 #include "dtc_common.h"
+#include "iou_threshold.h"
 #include "soft_nms_walk.h"
+#include "wave_ops.h"
 
 namespace dtc {
 
@@ -63,8 +65,6 @@ __global__ __launch_bounds__(kSortThreads) void segment_sort_desc_kernel(
 // 2. suppression-matrix tiles.  boxes [S, n_stride, 4] score-sorted; mask [S, n_stride, ncb_stride] u64, only tiles with
 //    cb >= rb are written (and only those are read).
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float box_area(float4 b) { return (b.z - b.x + 1.f) * (b.w - b.y + 1.f); }  // cython_nms.pyx:44
-
 // v_max_f32 / v_min_f32 on operands that come straight from memory.  fmaxf() makes the compiler canonicalise such operands
 // first (v_max x, x, x: signalling NaNs), one extra instruction per LDS-broadcast row coordinate and pair; the hardware
 // instruction in IEEE mode already quiets them, and for everything that is not a signalling NaN the result is the same.
@@ -150,14 +150,9 @@ __global__ __launch_bounds__(64 * kMaskWaves) void nms_mask_kernel(const float4*
         const float xx2 = vmin(r.z, cbox.z), yy2 = vmin(r.w, cbox.w);            // :78-79
         const float w = fmaxf(0.0f, xx2 - xx1 + 1.f), h = fmaxf(0.0f, yy2 - yy1 + 1.f);  // :80-81
         const float inter = w * h;                                               // :82
-        // :83-84  `inter / (iarea + areas[j] - inter) >= thresh` with an IEEE float division.  Rounding is monotone, so the
-        // rounded quotient is >= thresh whenever the exact one is, and < thresh whenever the exact one is below
-        // thresh * (1 - 2^-24): the division itself is needed only if inter - thresh * u cannot be signed reliably.
-        // d = fl(inter - fl(thresh * u)) carries <= 2^-23 * pu of error, so outside the band |d| <= 2^-21 * pu its sign IS the
-        // answer: five instructions and ONE compare per pair, and that compare is the ballot mask itself.  (The previous form
-        // -- two scaled products, three compares -- made the compiler rebuild the mask with a 0/1 select + re-compare.)
-        // u <= 0 (degenerate boxes), thresh <= 0 and the band take the division, exactly like the reference; they are decided
-        // per wavefront (a uniform branch: about one pair in 10^6 is that close to the threshold).
+        // :83-84  `inter / (iarea + areas[j] - inter) >= thresh`: iou_band of iou_threshold.h (the derivation is there), spelled out
+        // with vmin so that the one compare per pair is the ballot mask itself.  (The previous form -- two scaled products, three
+        // compares -- made the compiler rebuild the mask with a 0/1 select + re-compare.)
         const float u = iarea + carea - inter;
         const float pu = thresh * u;
         const float d = inter - pu;
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(64) void nms_reduce_kernel(const uint64_t* __restri
       kept += __builtin_popcountll(keepw);
     }
     if ((keepw >> lane) & 1ull) {
-      const int before = __builtin_popcountll(keepw & ((1ull << lane) - 1ull));
+      const int before = lanes_below(keepw, lane);
       K[kept - __builtin_popcountll(keepw) + before] = rb * 64 + lane;
     }
     if (rb + 1 < ncb && kept < cap) {
@@ -433,7 +428,7 @@ __global__ __launch_bounds__(kReduceLdsThreads) void nms_reduce_lds_kernel(const
       }
     }
     if ((keepw >> lane) & 1ull) {               // off the chain: the kept positions of this block leave after the OR is issued
-      const int before = __builtin_popcountll(keepw & ((1ull << lane) - 1ull));
+      const int before = lanes_below(keepw, lane);
       K[kept - __builtin_popcountll(keepw) + before] = rb * 64 + lane;
     }
     // LDS operations of one wavefront retire in order; the compiler must not carry `removed` across in registers
@@ -460,19 +455,38 @@ __global__ __launch_bounds__(kSortThreads) void nms_finalize_kernel(const int32_
   if (threadIdx.x == 0) *out_count = n;
 }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Workspace layouts: the *_workspace_bytes entries answer with `total`, the launchers carve by the offsets.
+struct NmsSortedPlan { size_t mask, diag_t, next_counts, total; };
+static NmsSortedPlan nms_sorted_plan(int n_seg, int n_stride) {
+  NmsSortedPlan d;
+  const size_t ncb = (size_t)(n_stride + 63) / 64;
+  Carve w{256};
+  d.mask = w.take((size_t)n_seg * n_stride * ncb * sizeof(uint64_t));        // suppression matrix [n_seg][n_stride][ncb]
+  d.diag_t = w.take((size_t)n_seg * n_stride * sizeof(uint64_t));            // transposed diagonal tiles [n_seg][n_stride]
+  d.next_counts = w.take((size_t)n_seg * sizeof(int32_t));                   // the counts the second phase of a keep[:max_keep] call runs on
+  d.total = w.end;
+  return d;
+}
+
+struct NmsPlan { size_t sorted_boxes, order, keep, count, sorted_ws, sorted_ws_bytes, total; };
+static NmsPlan nms_plan(int n) {
+  NmsPlan d;
+  Carve w{256};
+  d.sorted_boxes = w.take((size_t)n * 4 * sizeof(float));
+  d.order = w.take((size_t)n * sizeof(int32_t));
+  d.keep = w.take((size_t)n * sizeof(int32_t));                              // kept positions
+  d.count = w.take(sizeof(int32_t));
+  d.sorted_ws_bytes = nms_sorted_plan(1, n).total;                         // dtc_nms_sorted's own workspace
+  d.sorted_ws = w.take(d.sorted_ws_bytes);
+  d.total = w.end;
+  return d;
+}
 
 }  // namespace dtc
 
 // ---- C ABI ----------------------------------------------------------------------------------------------------------
 
-DTC_API size_t dtc_nms_sorted_workspace_bytes(int n_seg, int n_stride) {
-  const size_t ncb = (size_t)(n_stride + 63) / 64;
-  // suppression matrix [n_seg][n_stride][ncb] + transposed diagonal tiles [n_seg][n_stride]
-  // + the per-segment counts the second phase of a keep[:max_keep] call runs on
-  return dtc::align_up((size_t)n_seg * n_stride * ncb * sizeof(uint64_t), 256) +
-         dtc::align_up((size_t)n_seg * n_stride * sizeof(uint64_t), 256) + dtc::align_up((size_t)n_seg * sizeof(int32_t), 256);
-}
+DTC_API size_t dtc_nms_sorted_workspace_bytes(int n_seg, int n_stride) { return dtc::nms_sorted_plan(n_seg, n_stride).total; }
 
 DTC_API int dtc_nms_sorted(const float* boxes, const int32_t* counts, int n_seg, int n_stride, float thresh,
                            int max_keep, void* workspace, size_t workspace_bytes, int32_t* keep, int keep_stride,
@@ -482,13 +496,14 @@ DTC_API int dtc_nms_sorted(const float* boxes, const int32_t* counts, int n_seg,
   if (!keep_count || (n_stride > 0 && (!boxes || !keep || !workspace))) return DTC_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (n_stride == 0) { return dtc::zero_async(keep_count, sizeof(int32_t) * n_seg, s); }
-  if (workspace_bytes < dtc_nms_sorted_workspace_bytes(n_seg, n_stride)) return DTC_EWORKSPACE;
+  const dtc::NmsSortedPlan pl = dtc::nms_sorted_plan(n_seg, n_stride);
+  if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
   const int ncb = (n_stride + 63) / 64;
   if (ncb > 64 * 4) return DTC_EUNSUPPORTED;  // > 16384 boxes per segment
-  uint64_t* mask = reinterpret_cast<uint64_t*>(workspace);
-  uint64_t* diag_t = reinterpret_cast<uint64_t*>(reinterpret_cast<unsigned char*>(workspace) +
-                                                 dtc::align_up((size_t)n_seg * n_stride * ((n_stride + 63) / 64) * sizeof(uint64_t), 256));
-  int32_t* next_counts = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(diag_t) + dtc::align_up((size_t)n_seg * n_stride * sizeof(uint64_t), 256));
+  unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
+  uint64_t* mask = reinterpret_cast<uint64_t*>(w + pl.mask);
+  uint64_t* diag_t = reinterpret_cast<uint64_t*>(w + pl.diag_t);
+  int32_t* next_counts = reinterpret_cast<int32_t*>(w + pl.next_counts);
   // tile groups on or above the diagonal of a segment of ncb_ column blocks (see the kernel)
   auto upper_groups = [](int ncb_) {
     const int ncg = (ncb_ + dtc::kMaskWaves - 1) / dtc::kMaskWaves;
@@ -561,13 +576,7 @@ DTC_API int dtc_segment_sort_desc(const float* scores, int score_stride_elems, c
 
 // Drop-in for cython_nms.nms(dets[N,5] float32, thresh) (lib/utils_cython/cython_nms.pyx:37): device in, device out.
 // keep_out int64 [n] receives ascending original indices, keep_count int32 [1] their number.
-DTC_API size_t dtc_nms_workspace_bytes(int n) {
-  const size_t a = dtc::align_up((size_t)n * 4 * sizeof(float), 256);    // sorted boxes
-  const size_t b = dtc::align_up((size_t)n * sizeof(int32_t), 256);      // order
-  const size_t c = dtc::align_up((size_t)n * sizeof(int32_t), 256);      // keep positions
-  const size_t d = 256;                                                  // count
-  return a + b + c + d + dtc_nms_sorted_workspace_bytes(1, n);
-}
+DTC_API size_t dtc_nms_workspace_bytes(int n) { return dtc::nms_plan(n).total; }
 
 DTC_API int dtc_nms(const float* dets, int n, float thresh, void* workspace, size_t workspace_bytes, int64_t* keep_out,
                     int32_t* keep_count, dtc_stream_t stream) {
@@ -576,15 +585,16 @@ DTC_API int dtc_nms(const float* dets, int n, float thresh, void* workspace, siz
   if (n == 0) return dtc::zero_async(keep_count, sizeof(int32_t), s);  // boxes.py:334-335
   if (n > 16384) return DTC_EUNSUPPORTED;
   if (!dets || !keep_out || !workspace) return DTC_EINVAL;
-  if (workspace_bytes < dtc_nms_workspace_bytes(n)) return DTC_EWORKSPACE;
+  const dtc::NmsPlan pl = dtc::nms_plan(n);
+  if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-  float* sboxes = reinterpret_cast<float*>(w); w += dtc::align_up((size_t)n * 4 * sizeof(float), 256);
-  int32_t* order = reinterpret_cast<int32_t*>(w); w += dtc::align_up((size_t)n * sizeof(int32_t), 256);
-  int32_t* keep = reinterpret_cast<int32_t*>(w); w += dtc::align_up((size_t)n * sizeof(int32_t), 256);
-  int32_t* cnt = reinterpret_cast<int32_t*>(w); w += 256;
+  float* sboxes = reinterpret_cast<float*>(w + pl.sorted_boxes);
+  int32_t* order = reinterpret_cast<int32_t*>(w + pl.order);
+  int32_t* keep = reinterpret_cast<int32_t*>(w + pl.keep);
+  int32_t* cnt = reinterpret_cast<int32_t*>(w + pl.count);
   int rc = dtc_segment_sort_desc(dets + 4, 5, dets, 5, nullptr, 1, n, order, sboxes, nullptr, stream);
   if (rc != DTC_OK) return rc;
-  rc = dtc_nms_sorted(sboxes, nullptr, 1, n, thresh, 0, w, dtc_nms_sorted_workspace_bytes(1, n), keep, n, cnt, stream);
+  rc = dtc_nms_sorted(sboxes, nullptr, 1, n, thresh, 0, w + pl.sorted_ws, pl.sorted_ws_bytes, keep, n, cnt, stream);
   if (rc != DTC_OK) return rc;
   const size_t smem = (size_t)dtc::next_pow2(n) * sizeof(uint64_t);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
@@ -639,48 +649,6 @@ DTC_API int dtc_soft_nms(const float* dets, int n, float sigma, float overlap_th
   if (dtc::raise_lds_once<dtc::soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   hipLaunchKernelGGL(dtc::soft_nms_kernel, dim3(1), dim3(64), smem, s, dets, n, sigma, overlap_thresh, score_thresh, method,
                      dets_out, inds_out, n_out);
-  DTC_CHECK_LAUNCH();
-  return DTC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// A4 (numpy flavour)  bbox_transform + clip_tiled_boxes for ALL classes -- lib/utils/boxes.py:168-208 and :150-165.
-// The fused detection kernel decodes only the (roi, class) pairs that pass the score threshold; this entry exists for
-// callers of the stand-alone box_utils functions.
-// ---------------------------------------------------------------------------------------------------------------------
-namespace dtc {
-__global__ void bbox_transform_kernel(const float* __restrict__ boxes, const float* __restrict__ deltas, int n, int n_cls,
-                                      float wx, float wy, float ww, float wh, int do_clip, float im_h, float im_w,
-                                      float* __restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * n_cls) return;
-  const int i = t / n_cls;
-  const float* b = boxes + (size_t)i * 4;
-  const float* d = deltas + (size_t)t * 4;
-  const float widths = b[2] - b[0] + 1.0f, heights = b[3] - b[1] + 1.0f;          // boxes.py:178-179
-  const float ctr_x = b[0] + 0.5f * widths, ctr_y = b[1] + 0.5f * heights;        // :180-181
-  const float dx = fdiv(d[0], wx), dy = fdiv(d[1], wy);                           // :184-185
-  float dw = fdiv(d[2], ww), dh = fdiv(d[3], wh);                                 // :186-187
-  dw = fminf(dw, 4.135166556742356f); dh = fminf(dh, 4.135166556742356f);         // :190-191
-  const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;              // :193-194
-  const float pw = fexp_cr(dw) * widths, ph = fexp_cr(dh) * heights;              // :195-196
-  float o0 = pcx - 0.5f * pw, o1 = pcy - 0.5f * ph, o2 = pcx + 0.5f * pw - 1.f, o3 = pcy + 0.5f * ph - 1.f;  // :200-206
-  if (do_clip) {                                                                  // :158-164
-    o0 = fmaxf(fminf(o0, im_w - 1.f), 0.f); o1 = fmaxf(fminf(o1, im_h - 1.f), 0.f);
-    o2 = fmaxf(fminf(o2, im_w - 1.f), 0.f); o3 = fmaxf(fminf(o3, im_h - 1.f), 0.f);
-  }
-  reinterpret_cast<float4*>(out)[t] = make_float4(o0, o1, o2, o3);
-}
-}  // namespace dtc
-
-DTC_API int dtc_bbox_transform(const float* boxes, const float* deltas, int n, int n_cls, float wx, float wy, float ww,
-                               float wh, int do_clip, float im_h, float im_w, float* out, dtc_stream_t stream) {
-  if (n < 0 || n_cls < 1) return DTC_EINVAL;
-  if (n == 0) return DTC_OK;
-  if (!boxes || !deltas || !out) return DTC_EINVAL;
-  const long long total = (long long)n * n_cls;
-  hipLaunchKernelGGL(dtc::bbox_transform_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), boxes, deltas, n, n_cls, wx, wy, ww, wh, do_clip, im_h, im_w, out);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }

@@ -9,6 +9,7 @@
 
 #include "block_sort.h"
 #include "dtc_common.h"
+#include "wave_ops.h"
 
 namespace dtc {
 
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(kPrepThreads) void proposal_dedup_kernel(PrepParams
     __syncthreads();
     int rank = run_s;
     for (int q = 0; q < wv; q++) rank += wave_heads[q];
-    rank += __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    rank += lanes_below(m, lane);
     if (head && rank < p.max_out) {
       const int i = (int)(k & ((1u << kIdxBits) - 1u));
       reinterpret_cast<float4*>(p.uniq)[(size_t)b * p.max_out + rank] = scaled_row(p, b, i, s);
@@ -98,13 +99,22 @@ __global__ __launch_bounds__(kPrepThreads) void proposal_dedup_kernel(PrepParams
   if (tid == 0) p.n_uniq[b] = min(run_s, p.max_out);
 }
 
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// workspace layout: the unique rows between the two launches, and their number per image
+struct PrepPlan { size_t uniq, n_uniq, total; };
+static PrepPlan prep_plan(int batch, int max_out) {
+  PrepPlan d;
+  Carve w{16};
+  d.uniq = w.take((size_t)batch * max_out * 4 * sizeof(float));
+  d.n_uniq = w.take((size_t)(batch > 0 ? batch : 1) * sizeof(int32_t));
+  d.total = w.end;
+  return d;
+}
 
 }  // namespace dtc
 
 DTC_API size_t dtc_prepare_proposals_workspace_bytes(int batch, int max_out) {
   if (batch < 0 || max_out < 1) return 0;
-  return dtc::align16((size_t)batch * max_out * 4 * sizeof(float)) + dtc::align16((size_t)(batch > 0 ? batch : 1) * sizeof(int32_t));
+  return dtc::prep_plan(batch, max_out).total;
 }
 
 DTC_API int dtc_prepare_proposals(const float* boxes, const int32_t* counts, const float* im_scale, int batch, int in_stride,
@@ -121,12 +131,13 @@ DTC_API int dtc_prepare_proposals(const float* boxes, const int32_t* counts, con
       !workspace)
     return DTC_EINVAL;
   if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(boxes) & 15) != 0) return DTC_EINVAL;
-  if (workspace_bytes < dtc_prepare_proposals_workspace_bytes(batch, max_out)) return DTC_EWORKSPACE;
+  const dtc::PrepPlan pl = dtc::prep_plan(batch, max_out);
+  if (workspace_bytes < pl.total) return DTC_EWORKSPACE;
   dtc::PrepParams p;
   p.boxes = boxes; p.counts = counts; p.im_scale = im_scale; p.in_stride = in_stride; p.max_out = max_out;
   p.dedup_scale = dedup_scale;
-  p.uniq = reinterpret_cast<float*>(workspace);
-  p.n_uniq = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + dtc::align16((size_t)batch * max_out * 4 * sizeof(float)));
+  p.uniq = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.uniq);
+  p.n_uniq = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + pl.n_uniq);
   p.src_index = src_index;
   hipLaunchKernelGGL(dtc::proposal_dedup_kernel, dim3(batch), dim3(dtc::kPrepThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
   DTC_CHECK_LAUNCH();

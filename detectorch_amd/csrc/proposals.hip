@@ -274,6 +274,7 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
 // generate_proposals.py:165-214 (weights (1,1,1,1)) + :216-238 + :151-163
 // torch.min / torch.max propagate NaN (fminf / fmaxf would return the other operand): the compares below are false on NaN, so a
 // NaN delta gives a NaN box, which fails filter_boxes (:159-162) as it does in the reference.  -0 clips to +0, as oracle.c does.
+// (Not box_decode.h's decode_clip on purpose: that one is numpy's decode, whose fminf / fmaxf drop a NaN operand.)
 __device__ __forceinline__ float clip1(float v, float hi) { v = v >= hi ? hi : v; return v <= 0.f ? 0.f : v; }
 
 __device__ __forceinline__ void decode_box(float ax1, float ay1, float ax2, float ay2, float dx, float dy, float dw,
@@ -513,8 +514,6 @@ __global__ void rpn_gather_kept_kernel(const float4* __restrict__ boxes, const f
   out_scores[(size_t)seg * keep_stride + i] = scores[(size_t)seg * k_stride + src];
 }
 
-static inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-
 struct RpnPlan {
   int chunks_per_image, ties_per_image, k_stride, n_seg, dec_blocks;
   size_t off_hist, off_counters, off_ticket, off_blk, off_gt, off_tie, off_sorted, off_nrank, total;
@@ -544,18 +543,18 @@ static int make_plan(const dtc_rpn_level* levels, int n_levels, int batch, int k
   if (k_stride < kmax) return DTC_EINVAL;
   const int S = batch * n_levels;
   plan->chunks_per_image = chunks; plan->ties_per_image = ties; plan->k_stride = k_stride; plan->n_seg = S;
-  size_t o = 0;
+  Carve w{256};
   plan->dec_blocks = (k_stride + kDecodeThreads - 1) / kDecodeThreads;
   // [histograms | counters | tickets | block counts]: ONE clearing launch covers everything up to off_gt
-  plan->off_hist = o; o += al((size_t)S * 2 * kHistBins * sizeof(uint32_t));
-  plan->off_counters = o; o += al((size_t)S * 2 * sizeof(uint32_t));
-  plan->off_ticket = o; o += al((size_t)S * sizeof(uint32_t));
-  plan->off_blk = o; o += al((size_t)S * plan->dec_blocks * sizeof(uint32_t));
-  plan->off_gt = o; o += al((size_t)S * k_stride * sizeof(uint64_t));
-  plan->off_tie = o; o += al((size_t)batch * ties * sizeof(uint64_t));
-  plan->off_sorted = o; o += al((size_t)S * k_stride * sizeof(uint64_t));
-  plan->off_nrank = o; o += al((size_t)S * sizeof(int32_t));
-  plan->total = o;
+  plan->off_hist = w.take((size_t)S * 2 * kHistBins * sizeof(uint32_t));
+  plan->off_counters = w.take((size_t)S * 2 * sizeof(uint32_t));
+  plan->off_ticket = w.take((size_t)S * sizeof(uint32_t));
+  plan->off_blk = w.take((size_t)S * plan->dec_blocks * sizeof(uint32_t));
+  plan->off_gt = w.take((size_t)S * k_stride * sizeof(uint64_t));
+  plan->off_tie = w.take((size_t)batch * ties * sizeof(uint64_t));
+  plan->off_sorted = w.take((size_t)S * k_stride * sizeof(uint64_t));
+  plan->off_nrank = w.take((size_t)S * sizeof(int32_t));
+  plan->total = w.end;
   return DTC_OK;
 }
 
