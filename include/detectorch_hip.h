@@ -420,9 +420,14 @@ int dtc_postprocess_detections_ex2(const float* rois5, const int32_t* n_rois, co
  * Outputs: mask_boxes int32 [B,max_out,4] expanded+truncated ref box (:183-184); mask_rects int32 [B,max_out,4] paste
  * rectangle (x_0,y_0,x_1,y_1) (:204-207); crops uint8 [B,per_image_capacity]: for detection d the binarised resized mask
  * restricted to its paste rectangle, row-major, at byte mask_offsets[b,d] of image b's region; mask_bytes int64 [B] =
- * bytes image b needs (if > per_image_capacity the detections that did not fit were skipped).  mask_bytes is rewritten on every
- * call; rows d >= min(det_count[b], max_out) of mask_boxes / mask_rects / mask_offsets and the crop bytes outside the pasted
- * rectangles are unspecified.  masks rows of detections d >= min(det_count[b], max_out) are never read. */
+ * bytes image b needs, whatever the capacity.  mask_offsets[b,d] is the sum of the rectangle areas of the image's detections in
+ * front of d.  A detection is pasted iff mask_offsets[b,d] + area <= per_image_capacity (mask_bytes[b] > per_image_capacity: some
+ * were not); the others are skipped, their rows of mask_boxes / mask_rects / mask_offsets are still written, and no byte outside
+ * the pasted rectangles -- of this image's region, of another image's, or behind the last region -- is written.  mask_bytes is
+ * rewritten on every call; rows d >= min(det_count[b], max_out) of mask_boxes / mask_rects / mask_offsets are unspecified; the
+ * crop bytes outside the pasted rectangles keep what the caller left there.  masks rows of detections d >= min(det_count[b], max_out)
+ * are never read.  cls_specific_mask 0: channel 0 of the detection's mask row, whatever its class (:192-195).  im_size is
+ * truncated to integers.  M + 2 <= 64 (DTC_EINVAL beyond, and for M < 1). */
 int dtc_mask_paste(const float* masks, const int32_t* mask_index, int n_cls, int M, const float* dets,
                    const int32_t* det_count, const float* im_size, int batch, int max_out, float thresh_binarize,
                    int cls_specific_mask, uint8_t* crops, long long per_image_capacity, int32_t* mask_boxes,
@@ -433,10 +438,14 @@ int dtc_mask_paste(const float* masks, const int32_t* mask_index, int n_cls, int
  * crops / mask_rects / mask_offsets without materialising the (im_h, im_w) frame.  Per detection (b, d):
  *   rle_counts uint32 [B,max_out,runs_stride]  run lengths (column-major, first run = zeros), rle_n_runs int32 [B,max_out]
  *   rle_str    uint8  [B,max_out,str_stride]   the compressed "counts" string (ASCII, no terminator), rle_str_len int32
- * A detection whose runs (string) do not fit gets rle_n_runs = -(runs needed) (rle_str_len = -(bytes needed)) and no
- * valid data: re-run with larger strides or encode that one on the host.  A detection whose crop did not fit
- * per_image_capacity (dtc_mask_paste skipped it: mask_bytes[b] > capacity) gets -1 / -1.  d >= det_count[b]: 0 / 0, rewritten on
- * every call.  rle_counts / rle_str past each row's length are unspecified. */
+ * A detection whose runs do not fit runs_stride gets rle_n_runs = -(runs needed) and rle_str_len = -1 (the string is not formed,
+ * so its length is not known: 7 bytes per run always suffice), and no valid data.  One whose runs fit and whose string does not
+ * fit str_stride gets rle_n_runs = runs (> 0, rle_counts valid) and rle_str_len = -(bytes needed).  Either way: re-run with
+ * larger strides or encode that one on the host.  A detection with mask_offsets[b,d] + area > per_image_capacity
+ * (dtc_mask_paste skipped it) gets -1 / -1; a zero-area rectangle therefore gets -1 / -1 when its offset is above the capacity
+ * and, like every empty rectangle that fits, one run of im_h * im_w zeros when its offset is at most the capacity.
+ * d >= det_count[b]: 0 / 0, rewritten on every call.  Nothing is written past a row's runs_stride / str_stride, or to the rows
+ * d >= det_count[b] of rle_counts / rle_str; rle_counts / rle_str past each row's length are unspecified. */
 int dtc_mask_rle(const uint8_t* crops, long long per_image_capacity, const int32_t* mask_rects,
                  const long long* mask_offsets, const int32_t* det_count, const float* im_size, int batch, int max_out,
                  uint32_t* rle_counts, int runs_stride, int32_t* rle_n_runs, uint8_t* rle_str, int str_stride,
