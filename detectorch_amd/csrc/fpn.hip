@@ -20,6 +20,11 @@ DTC_PT_TABLE(fpn)
 
 constexpr int kFpnThreads = 1024;
 constexpr int kFpnMaxLevels = 8;
+// LDS of the general kernel: the dynamic limit it is raised to, and its static arrays (lvl_off, in_off, wave_cnt, lvl_run).  The
+// host refuses a shape whose dynamic need + the static arrays exceed the limit (fpn_collect_launch).
+constexpr size_t kFpnGeneralLdsLimit = 144 * 1024;
+constexpr size_t kFpnGeneralStaticLds =
+    sizeof(int) * (2 * (kFpnMaxLevels + 1) + kFpnMaxLevels * (kFpnThreads / 64) + kFpnMaxLevels);      // 616 bytes
 
 struct FpnParams {
   const float* in_boxes;     // [B, L_in, P, 4]
@@ -532,8 +537,11 @@ static int fpn_collect_launch(dtc::FpnParams p, int batch, long long n_max, dtc_
     }
   }
   if (p.keep) return DTC_EUNSUPPORTED;         // the keep form exists in the fast kernel only: dtc_gather_kept + dtc_fpn_collect_distribute
+  // the general kernel's dynamic LDS on top of its static arrays must stay inside the limit it is raised to below: a larger shape
+  // (top_n > 8192 with a visiting order, or 8 * top_n + 4 * n_max past the budget with sorted inputs) is refused here, not at launch
+  if (smem > dtc::kFpnGeneralLdsLimit - dtc::kFpnGeneralStaticLds) return DTC_EUNSUPPORTED;
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    if (dtc::raise_lds_once<dtc::fpn_collect_distribute_kernel>(144 * 1024) != DTC_OK) return DTC_ELAUNCH;
+    if (dtc::raise_lds_once<dtc::fpn_collect_distribute_kernel>((int)dtc::kFpnGeneralLdsLimit) != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::fpn_collect_distribute_kernel, dim3(batch), dim3(dtc::kFpnThreads), smem, s, p);
   DTC_CHECK_LAUNCH();

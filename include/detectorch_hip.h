@@ -209,6 +209,11 @@ int dtc_gather_kept(const float* sorted_boxes, const float* sorted_scores, int n
  *   dtc_roi_align_forward_packed.
  * inputs_sorted != 0 promises that every input list is already in descending score order (true for NMS output): the
  * lists are then merged by rank instead of sorted.
+ * Limits (DTC_EUNSUPPORTED): post_nms_top_n > 16384; with scores, n_in_levels * in_stride > 16384; and, for the shapes the merge
+ * kernel does not take (post_nms_top_n > 2048, in_stride > 1024, n_in_levels * in_stride > 8192, its buffers past 150 KB, or
+ * unsorted lists), whatever the general kernel's 144 KB of workgroup memory less its 616 bytes of tables cannot hold:
+ *   with roi_order, 16 * max(4, next_pow2(post_nms_top_n)) bytes, i.e. post_nms_top_n > 8192;
+ *   with sorted lists, 8 * post_nms_top_n + 4 * n_in_levels * in_stride + 16 bytes (16384 rows of input: post_nms_top_n > 10161).
  * Rewritten on every call, whatever the previous call left: n_out, level_counts, roi_levels (all topN rows: -1 past n_out),
  * roi_order (all topN rows: a permutation of b*topN + [0, topN)) and roi_desc (all topN rows: padding rows carry level -1, so
  * RoIAlign zero-fills their output rows).  Rows >= n_out[b] of rois5, roi_scores, rois_by_level and idx_restore are unspecified. */
