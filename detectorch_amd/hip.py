@@ -91,109 +91,135 @@ def det_options_scoring(options=None):
     return det_options(**d), (scoring if d.get('do_bbox_vote') else None)
 
 
+# One row per exported function of include/detectorch_hip.h: return kind, entry(parameter[:kind] ...), with the header's names in
+# the header's order.  Return kinds: status (int DTC_* code, checked), int (plain: 0 can mean an error, the reference's convention),
+# size (size_t), str (const char*), void.  Parameter kinds: a pointer (any T*, dtc_stream_t) unless marked i int, f float, z size_t,
+# q long long, or with the ctypes class of a "const dtc_x*" struct pointer.  tests/test_binding_signatures_host.py holds the rows
+# to the header.
+_SIGNATURES = """
+str dtc_version()
+str dtc_target_arch()
+int launch_roi_align_forward_hip(outputElements:i bottom_data bottom_rois spatial_scale:f channels:i height:i width:i
+    pooled_height:i pooled_width:i sampling_ratio:i top_data stream)
+status dtc_roi_align_forward(levels:FeatLevel n_levels:i channels:i in_dtype:i rois roi_cols:i roi_levels n_rois:i pooled_h:i
+    pooled_w:i sampling_ratio:i out out_dtype:i stream)
+status dtc_roi_align_forward_ordered(levels:FeatLevel n_levels:i channels:i in_dtype:i rois roi_cols:i roi_levels roi_order n_rois:i
+    pooled_h:i pooled_w:i sampling_ratio:i out out_dtype:i stream)
+status dtc_roi_align_forward_packed(levels:FeatLevel n_levels:i channels:i in_dtype:i roi_desc n_rois:i pooled_h:i pooled_w:i
+    sampling_ratio:i out out_dtype:i stream)
+size dtc_roi_align_workspace_bytes(n_rois:i)
+void dtc_roi_align_set_exact(exact:i)
+int dtc_roi_align_get_exact()
+status dtc_roi_align_forward_packed_ws(levels:FeatLevel n_levels:i channels:i in_dtype:i roi_desc n_rois:i pooled_h:i pooled_w:i
+    sampling_ratio:i out out_dtype:i workspace workspace_bytes:z stream)
+size dtc_nms_workspace_bytes(n:i)
+status dtc_nms(dets n:i thresh:f workspace workspace_bytes:z keep_out keep_count stream)
+size dtc_nms_sorted_workspace_bytes(n_seg:i n_stride:i)
+status dtc_nms_sorted(boxes counts n_seg:i n_stride:i thresh:f max_keep:i workspace workspace_bytes:z keep keep_stride:i keep_count
+    stream)
+status dtc_segment_sort_desc(scores score_stride_elems:i boxes box_stride_elems:i counts n_seg:i n_stride:i order sorted_boxes
+    sorted_scores stream)
+size dtc_rpn_topk_decode_workspace_bytes(levels:RpnLevel n_levels:i batch:i k_stride:i)
+status dtc_rpn_topk_decode(levels:RpnLevel n_levels:i batch:i im_h:f im_w:f min_size_scaled:f workspace workspace_bytes:z out_boxes
+    out_scores out_counts k_stride:i stream)
+status dtc_rpn_topk_decode_sized(levels:RpnLevel n_levels:i batch:i im_h:f im_w:f im_hw min_size_scaled:f workspace
+    workspace_bytes:z out_boxes out_scores out_counts k_stride:i stream)
+status dtc_gather_kept(sorted_boxes sorted_scores n_seg:i k_stride:i keep keep_count keep_stride:i out_boxes out_scores stream)
+status dtc_fpn_collect_distribute(in_boxes in_scores in_counts batch:i n_in_levels:i in_stride:i post_nms_top_n:i k_min:i k_max:i
+    rois5 roi_scores roi_levels n_out rois_by_level level_counts idx_restore roi_order roi_desc inputs_sorted:i stream)
+status dtc_fpn_collect_distribute_kept(sorted_boxes sorted_scores k_stride:i keep keep_count keep_stride:i batch:i n_in_levels:i
+    post_nms_top_n:i k_min:i k_max:i rois5 roi_scores roi_levels n_out rois_by_level level_counts idx_restore roi_order roi_desc
+    stream)
+size dtc_prepare_proposals_workspace_bytes(batch:i max_out:i)
+status dtc_prepare_proposals(boxes counts im_scale batch:i in_stride:i dedup_scale:f k_min:i k_max:i max_out:i workspace
+    workspace_bytes:z rois5 roi_levels n_out rois_by_level level_counts idx_restore roi_order roi_desc src_index stream)
+size dtc_postprocess_detections_workspace_bytes(batch:i max_rois:i n_cls:i)
+status dtc_postprocess_detections(rois5 n_rois cls_score bbox_pred scaling_factor im_size batch:i max_rois:i n_cls:i wx:f wy:f ww:f
+    wh:f score_thresh:f nms_thresh:f max_det:i workspace workspace_bytes:z dets det_roi det_rois_scaled det_count max_out:i stream)
+status dtc_postprocess_detections_logits(rois5 n_rois cls_logits bbox_pred scaling_factor im_size batch:i max_rois:i n_cls:i wx:f
+    wy:f ww:f wh:f score_thresh:f nms_thresh:f max_det:i workspace workspace_bytes:z dets det_roi det_rois_scaled det_count
+    max_out:i stream)
+status dtc_postprocess_detections_fpn(rois5 n_rois cls_score scores_are_logits:i bbox_pred scaling_factor im_size batch:i max_rois:i
+    n_cls:i wx:f wy:f ww:f wh:f score_thresh:f nms_thresh:f max_det:i workspace workspace_bytes:z dets det_roi det_rois_scaled
+    det_count max_out:i fpn:FpnMapOut stream)
+status dtc_box_results_nms_limit(scores boxes n_rois batch:i max_rois:i n_cls:i score_thresh:f nms_thresh:f max_det:i workspace
+    workspace_bytes:z dets det_roi det_count max_out:i stream)
+size dtc_postprocess_detections_ex_workspace_bytes(batch:i max_rois:i n_cls:i opt:DetOptions)
+status dtc_postprocess_detections_ex(rois5 n_rois cls_score scores_are_logits:i bbox_pred decoded_boxes scaling_factor im_size
+    batch:i max_rois:i n_cls:i wx:f wy:f ww:f wh:f score_thresh:f nms_thresh:f max_det:i opt:DetOptions workspace workspace_bytes:z
+    dets det_roi det_rois_scaled det_count max_out:i fpn:FpnMapOut stream)
+size dtc_postprocess_detections_ex2_workspace_bytes(batch:i max_rois:i n_cls:i opt:DetOptions scoring:VoteScoring)
+status dtc_postprocess_detections_ex2(rois5 n_rois cls_score scores_are_logits:i bbox_pred decoded_boxes scaling_factor im_size
+    batch:i max_rois:i n_cls:i wx:f wy:f ww:f wh:f score_thresh:f nms_thresh:f max_det:i opt:DetOptions scoring:VoteScoring
+    workspace workspace_bytes:z dets det_roi det_rois_scaled det_count max_out:i fpn:FpnMapOut stream)
+status dtc_mask_paste(masks mask_index n_cls:i M:i dets det_count im_size batch:i max_out:i thresh_binarize:f cls_specific_mask:i
+    crops per_image_capacity:q mask_boxes mask_rects mask_offsets mask_bytes stream)
+status dtc_mask_rle(crops per_image_capacity:q mask_rects mask_offsets det_count im_size batch:i max_out:i rle_counts runs_stride:i
+    rle_n_runs rle_str str_stride:i rle_str_len stream)
+status dtc_bbox_overlaps(boxes n:i box_cols:i query_boxes k:i query_cols:i overlaps stream)
+status dtc_box_voting(top_dets n_top:i all_dets n_all:i thresh:f top_dets_out n_voters stream)
+status dtc_box_voting_scored(top_dets n_top:i all_dets n_all:i thresh:f scoring:VoteScoring top_dets_out n_voters stream)
+status dtc_bias_act(x bias residual n:i c:i h:i w:i dtype:i channels_last:i relu:i residual_up2:i stream)
+status dtc_prep_plan(heights widths batch:i target_size:i max_size:i pad_stride:i im_scales out_hw blob_hw)
+status dtc_prep_images(images:Image batch:i pixel_means im_scales out_hw blob blob_h:i blob_w:i stream)
+status dtc_soft_nms(dets n:i sigma:f overlap_thresh:f score_thresh:f method:i dets_out inds_out n_out stream)
+status dtc_bbox_transform(boxes deltas n:i n_cls:i wx:f wy:f ww:f wh:f do_clip:i im_h:f im_w:f out stream)
+"""
+
+_KINDS = {"p": C.c_void_p, "i": C.c_int, "f": C.c_float, "z": C.c_size_t, "q": C.c_longlong}
+_RETURNS = {"status": C.c_int, "int": C.c_int, "size": C.c_size_t, "str": C.c_char_p, "void": None}
+
+
+def _pointer(v):
+    if type(v) is torch.Tensor:
+        return v.data_ptr()
+    data_ptr = getattr(v, "data_ptr", None)       # (a Parameter); None (NULL), a stream handle or a host ctypes array: itself
+    return v if data_ptr is None else data_ptr()
+
+
+def _as_is(v):
+    return v
+
+
+_CONVERT = {"p": _pointer, "i": int, "f": float, "z": int, "q": int}
+
+
+def signatures(rows, structs):
+    """The rows of a signature table -> {entry: (return kind, ((parameter, kind), ...), ((parameter, invoke's converter), ...))}; a
+    struct kind is its class in `structs`."""
+    table = {}
+    for row in rows.replace("\n    ", " ").strip().split("\n"):
+        ret, entry, params = row.replace("(", " ").rstrip(")").split(" ", 2)
+        params = tuple((n, k if k in _KINDS else structs[k]) for n, k in ((p + ":p").split(":")[:2] for p in params.split()))
+        table[entry] = (ret, params, tuple((n, _CONVERT.get(k, _as_is)) for n, k in params))
+    return table
+
+
+SIGNATURES = signatures(_SIGNATURES, {c.__name__: c for c in (FeatLevel, RpnLevel, FpnMapOut, DetOptions, VoteScoring, Image)})
+
+
+def typed(L, table):
+    """Install the argtypes / restype of every entry of `table` on the CDLL L."""
+    for entry, (ret, params, _) in table.items():
+        fn = getattr(L, entry)
+        fn.argtypes = [_KINDS[k] if k in _KINDS else C.POINTER(k) for _, k in params]
+        fn.restype = _RETURNS[ret]
+    return L
+
+
 _lib = None
 
 
 def lib():
     """Load the native library or fail loudly."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "detectorch_amd: %s is missing. Build it with `python -m detectorch_amd.build` (hipcc, gfx950). "
-            "There is no CPU/PyTorch fallback for the region-proposal hot path." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    p, i, f = C.c_void_p, C.c_int, C.c_float
-    L.dtc_version.restype = C.c_char_p
-    L.dtc_target_arch.restype = C.c_char_p
-    L.launch_roi_align_forward_hip.argtypes = [i, p, p, f, i, i, i, i, i, i, p, p]
-    L.launch_roi_align_forward_hip.restype = i
-    L.dtc_roi_align_forward.argtypes = [C.POINTER(FeatLevel), i, i, i, p, i, p, i, i, i, i, p, i, p]
-    L.dtc_roi_align_forward.restype = i
-    L.dtc_roi_align_set_exact.argtypes = [i]
-    L.dtc_roi_align_set_exact.restype = None
-    L.dtc_roi_align_get_exact.argtypes = []
-    L.dtc_roi_align_get_exact.restype = i
-    L.dtc_roi_align_forward_ordered.argtypes = [C.POINTER(FeatLevel), i, i, i, p, i, p, p, i, i, i, i, p, i, p]
-    L.dtc_roi_align_forward_ordered.restype = i
-    sz = C.c_size_t
-    L.dtc_nms_workspace_bytes.argtypes = [i]
-    L.dtc_nms_workspace_bytes.restype = sz
-    L.dtc_nms.argtypes = [p, i, f, p, sz, p, p, p]
-    L.dtc_nms.restype = i
-    L.dtc_nms_sorted_workspace_bytes.argtypes = [i, i]
-    L.dtc_nms_sorted_workspace_bytes.restype = sz
-    L.dtc_nms_sorted.argtypes = [p, p, i, i, f, i, p, sz, p, i, p, p]
-    L.dtc_nms_sorted.restype = i
-    L.dtc_segment_sort_desc.argtypes = [p, i, p, i, p, i, i, p, p, p, p]
-    L.dtc_segment_sort_desc.restype = i
-    L.dtc_rpn_topk_decode_workspace_bytes.argtypes = [C.POINTER(RpnLevel), i, i, i]
-    L.dtc_rpn_topk_decode_workspace_bytes.restype = sz
-    L.dtc_rpn_topk_decode.argtypes = [C.POINTER(RpnLevel), i, i, f, f, f, p, sz, p, p, p, i, p]
-    L.dtc_rpn_topk_decode.restype = i
-    L.dtc_rpn_topk_decode_sized.argtypes = [C.POINTER(RpnLevel), i, i, f, f, p, f, p, sz, p, p, p, i, p]
-    L.dtc_rpn_topk_decode_sized.restype = i
-    L.dtc_gather_kept.argtypes = [p, p, i, i, p, p, i, p, p, p]
-    L.dtc_gather_kept.restype = i
-    ll = C.c_longlong
-    L.dtc_fpn_collect_distribute.argtypes = [p, p, p, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, i, p]
-    L.dtc_fpn_collect_distribute_kept.argtypes = [p, p, i, p, p, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, p]
-    L.dtc_fpn_collect_distribute_kept.restype = i
-    L.dtc_prepare_proposals_workspace_bytes.argtypes = [i, i]
-    L.dtc_prepare_proposals_workspace_bytes.restype = sz
-    L.dtc_prepare_proposals.argtypes = [p, p, p, i, i, f, i, i, i, p, sz, p, p, p, p, p, p, p, p, p, p]
-    L.dtc_prepare_proposals.restype = i
-    L.dtc_roi_align_forward_packed.argtypes = [C.POINTER(FeatLevel), i, i, i, p, i, i, i, i, p, i, p]
-    L.dtc_roi_align_forward_packed.restype = i
-    L.dtc_roi_align_workspace_bytes.argtypes = [i]
-    L.dtc_roi_align_workspace_bytes.restype = C.c_size_t
-    L.dtc_roi_align_forward_packed_ws.argtypes = [C.POINTER(FeatLevel), i, i, i, p, i, i, i, i, p, i, p, C.c_size_t, p]
-    L.dtc_roi_align_forward_packed_ws.restype = i
-    L.dtc_fpn_collect_distribute.restype = i
-    L.dtc_postprocess_detections_workspace_bytes.argtypes = [i, i, i]
-    L.dtc_postprocess_detections_workspace_bytes.restype = sz
-    L.dtc_postprocess_detections.argtypes = [p, p, p, p, p, p, i, i, i, f, f, f, f, f, f, i, p, sz, p, p, p, p, i, p]
-    L.dtc_postprocess_detections.restype = i
-    L.dtc_postprocess_detections_logits.argtypes = L.dtc_postprocess_detections.argtypes
-    L.dtc_postprocess_detections_logits.restype = i
-    L.dtc_postprocess_detections_fpn.argtypes = [p, p, p, i, p, p, p, i, i, i, f, f, f, f, f, f, i, p, sz, p, p, p, p, i,
-                                                 C.POINTER(FpnMapOut), p]
-    L.dtc_postprocess_detections_fpn.restype = i
-    L.dtc_box_results_nms_limit.argtypes = [p, p, p, i, i, i, f, f, i, p, sz, p, p, p, i, p]
-    L.dtc_box_results_nms_limit.restype = i
-    L.dtc_postprocess_detections_ex_workspace_bytes.argtypes = [i, i, i, C.POINTER(DetOptions)]
-    L.dtc_postprocess_detections_ex_workspace_bytes.restype = sz
-    L.dtc_postprocess_detections_ex.argtypes = [p, p, p, i, p, p, p, p, i, i, i, f, f, f, f, f, f, i, C.POINTER(DetOptions), p,
-                                                sz, p, p, p, p, i, C.POINTER(FpnMapOut), p]
-    L.dtc_postprocess_detections_ex.restype = i
-    L.dtc_postprocess_detections_ex2_workspace_bytes.argtypes = [i, i, i, C.POINTER(DetOptions), C.POINTER(VoteScoring)]
-    L.dtc_postprocess_detections_ex2_workspace_bytes.restype = sz
-    L.dtc_postprocess_detections_ex2.argtypes = [p, p, p, i, p, p, p, p, i, i, i, f, f, f, f, f, f, i, C.POINTER(DetOptions),
-                                                 C.POINTER(VoteScoring), p, sz, p, p, p, p, i, C.POINTER(FpnMapOut), p]
-    L.dtc_postprocess_detections_ex2.restype = i
-    L.dtc_bias_act.argtypes = [p, p, p, i, i, i, i, i, i, i, i, p]
-    L.dtc_bias_act.restype = i
-    L.dtc_mask_paste.argtypes = [p, p, i, i, p, p, p, i, i, f, i, p, ll, p, p, p, p, p]
-    L.dtc_mask_paste.restype = i
-    L.dtc_mask_rle.argtypes = [p, ll, p, p, p, p, i, i, p, i, p, p, i, p, p]
-    L.dtc_mask_rle.restype = i
-    L.dtc_prep_plan.argtypes = [p, p, i, i, i, i, p, p, p]
-    L.dtc_prep_plan.restype = i
-    L.dtc_prep_images.argtypes = [C.POINTER(Image), i, p, p, p, p, i, i, p]
-    L.dtc_prep_images.restype = i
-    L.dtc_bbox_overlaps.argtypes = [p, i, i, p, i, i, p, p]
-    L.dtc_bbox_overlaps.restype = i
-    L.dtc_box_voting.argtypes = [p, i, p, i, f, p, p, p]
-    L.dtc_box_voting.restype = i
-    L.dtc_box_voting_scored.argtypes = [p, i, p, i, f, C.POINTER(VoteScoring), p, p, p]
-    L.dtc_box_voting_scored.restype = i
-    L.dtc_soft_nms.argtypes = [p, i, f, f, f, i, p, p, p, p]
-    L.dtc_soft_nms.restype = i
-    L.dtc_bbox_transform.argtypes = [p, p, i, i, f, f, f, f, i, f, f, p, p]
-    L.dtc_bbox_transform.restype = i
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                "detectorch_amd: %s is missing. Build it with `python -m detectorch_amd.build` (hipcc, gfx950). "
+                "There is no CPU/PyTorch fallback for the region-proposal hot path." % LIB_PATH)
+        _lib = typed(C.CDLL(LIB_PATH), SIGNATURES)
+    return _lib
 
 
 def check(rc, what):
@@ -203,6 +229,33 @@ def check(rc, what):
 
 def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def invoke(L, table, entry, args, what=None):
+    """L.entry with the keyword arguments `args` placed in the table's order; returns what it returns, a status entry's DTC_E* code
+    raises instead (check), naming `what` or the entry.  Pointers: a tensor gives its data_ptr(), None is NULL; int / float kinds go
+    through int() / float(); a ctypes struct or array is passed as the object it is.  A `stream` that is not given is the current
+    stream of the current device.  TypeError, before the library is touched, on a missing or unknown name."""
+    ret, params, convert = table[entry]
+    if "stream" not in args and params and params[-1][0] == "stream":
+        args["stream"] = stream_ptr()
+    try:
+        if len(args) != len(params):
+            raise KeyError
+        values = [c(args[n]) for n, c in convert]                  # (as many names as parameters and none missing: none unknown)
+    except KeyError:
+        names = [n for n, _ in params]
+        raise TypeError("%s: missing %s, unknown %s" % (entry, [n for n in names if n not in args],
+                                                        [n for n in args if n not in names])) from None
+    rc = getattr(L, entry)(*values)
+    if ret == "status":
+        check(rc, what or entry)
+    return rc
+
+
+def call(entry, what=None, /, **args):
+    """An entry of libdetectorch_hip.so by parameter name (invoke)."""
+    return invoke(lib(), SIGNATURES, entry, args, what)
 
 
 def _dtype_code(t):
@@ -271,9 +324,8 @@ def bias_act_(x, bias=None, residual=None, relu=True, residual_up2=False):
     elif residual_up2:
         raise ValueError("residual_up2 needs a residual")
     with torch.cuda.device(dev):      # like every other launcher: the kernel goes to x's device whatever the current one is
-        check(lib().dtc_bias_act(x.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                 residual.data_ptr() if residual is not None else None, n, c, h, w, _dtype_code(x.dtype), cl,
-                                 1 if relu else 0, 1 if residual_up2 else 0, stream_ptr(dev)), "dtc_bias_act")
+        call("dtc_bias_act", x=x, bias=bias, residual=residual, n=n, c=c, h=h, w=w, dtype=_dtype_code(x.dtype), channels_last=cl,
+             relu=bool(relu), residual_up2=bool(residual_up2))
     return x
 
 
@@ -282,7 +334,7 @@ def roi_align_set_exact(exact=True):
     sampling, single level) kernel may merge taps -- the same sums in exact arithmetic, <= 1e-5 from the reference in float32.
     Read by the host at LAUNCH time: a hipGraph keeps the mode it was captured with; shared by all threads / streams of the process
     (include/detectorch_hip.h)."""
-    lib().dtc_roi_align_set_exact(1 if exact else 0)
+    call("dtc_roi_align_set_exact", exact=bool(exact))
 
 
 def roi_align_forward(features, spatial_scales, rois, pooled_h, pooled_w, sampling_ratio, roi_levels=None,
@@ -312,14 +364,27 @@ def roi_align_forward(features, spatial_scales, rois, pooled_h, pooled_w, sampli
         out = torch.empty((R, ch, pooled_h, pooled_w), dtype=odt, device=dev)
     if roi_levels is not None:
         roi_levels = roi_levels.to(torch.int32).contiguous()
+    if roi_order is not None:
+        roi_order = roi_order.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
-        rc = lib().dtc_roi_align_forward_ordered(
-            lv, len(features), ch, _dtype_code(dt), rois.data_ptr(), cols if R else 5,
-            roi_levels.data_ptr() if roi_levels is not None else None,
-            roi_order.to(torch.int32).contiguous().data_ptr() if roi_order is not None else None, R, int(pooled_h),
-            int(pooled_w), int(sampling_ratio), out.data_ptr(), _dtype_code(odt), stream_ptr(dev))
-    check(rc, "dtc_roi_align_forward")
+        call("dtc_roi_align_forward_ordered", "dtc_roi_align_forward", levels=lv, n_levels=len(features), channels=ch,
+             in_dtype=_dtype_code(dt), rois=rois, roi_cols=cols if R else 5, roi_levels=roi_levels, roi_order=roi_order, n_rois=R,
+             pooled_h=pooled_h, pooled_w=pooled_w, sampling_ratio=sampling_ratio, out=out, out_dtype=_dtype_code(odt))
     return out
+
+
+def roi_align_packed(levels, channels, in_dtype, roi_desc, n_rois, pooled_h, pooled_w, sampling_ratio, out, ws=None, stream=None,
+                     what="roi_align(packed)"):
+    """dtc_roi_align_forward_packed -- with a workspace `ws`, dtc_roi_align_forward_packed_ws -- over a FeatLevel array (make_levels)
+    of in_dtype maps: the rows of roi_desc [n_rois,8] into out [n_rois,channels,pooled_h,pooled_w], on `stream` (None: the current
+    one).  No allocation and no device guard: the caller's."""
+    args = dict(levels=levels, n_levels=len(levels), channels=channels, in_dtype=_dtype_code(in_dtype), roi_desc=roi_desc,
+                n_rois=n_rois, pooled_h=pooled_h, pooled_w=pooled_w, sampling_ratio=sampling_ratio, out=out,
+                out_dtype=_dtype_code(out.dtype), stream=stream or stream_ptr(out.device))
+    if ws is None:
+        call("dtc_roi_align_forward_packed", what, **args)
+    else:
+        call("dtc_roi_align_forward_packed_ws", what, workspace=ws, workspace_bytes=ws.numel(), **args)
 
 
 def _ptr(t):
@@ -340,14 +405,11 @@ def nms(dets, thresh):
     dets = dets.contiguous()
     if dets.dtype != torch.float32 or dets.dim() != 2 or dets.shape[1] != 5:
         raise TypeError("dets must be float32 [N,5]")
-    L = lib()
-    ws = workspace(L.dtc_nms_workspace_bytes(n), dev)
+    ws = workspace(call("dtc_nms_workspace_bytes", n=n), dev)
     keep = torch.empty((n,), dtype=torch.int64, device=dev)
     cnt = torch.empty((1,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = L.dtc_nms(dets.data_ptr(), n, float(thresh), ws.data_ptr(), ws.numel(), keep.data_ptr(), cnt.data_ptr(),
-                       stream_ptr(dev))
-    check(rc, "dtc_nms")
+        call("dtc_nms", dets=dets, n=n, thresh=thresh, workspace=ws, workspace_bytes=ws.numel(), keep_out=keep, keep_count=cnt)
     return keep[:int(cnt.item())]
 
 
@@ -357,14 +419,12 @@ def nms_sorted(boxes, counts, thresh, max_keep=0, keep_stride=None):
     boxes = boxes.contiguous()
     S, N = boxes.shape[0], boxes.shape[1]
     ks = int(keep_stride or (max_keep if max_keep > 0 else N))
-    L = lib()
-    ws = workspace(L.dtc_nms_sorted_workspace_bytes(S, N), dev)
+    ws = workspace(call("dtc_nms_sorted_workspace_bytes", n_seg=S, n_stride=N), dev)
     keep = torch.empty((S, max(ks, 1)), dtype=torch.int32, device=dev)
     cnt = torch.empty((max(S, 1),), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = L.dtc_nms_sorted(boxes.data_ptr(), _ptr(counts), S, N, float(thresh), int(max_keep), ws.data_ptr(),
-                              ws.numel(), keep.data_ptr(), ks, cnt.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_nms_sorted")
+        call("dtc_nms_sorted", boxes=boxes, counts=counts, n_seg=S, n_stride=N, thresh=thresh, max_keep=max_keep, workspace=ws,
+             workspace_bytes=ws.numel(), keep=keep, keep_stride=ks, keep_count=cnt)
     return keep, cnt[:S]
 
 
@@ -405,7 +465,6 @@ def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w,
     own (h_b, w_b) blob gives; None: every image is (im_h, im_w).
     """
     dev = _require_cuda(*cls_probs, *bbox_preds)
-    L_ = lib()
     nl = len(cls_probs)
     B = cls_probs[0].shape[0]
     lv, alive = make_rpn_levels(cls_probs, bbox_preds, anchors, feat_strides, pre_nms_top_n, scores_are_logits)
@@ -415,17 +474,16 @@ def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w,
         K = N if (pre_nms_top_n[k] <= 0 or pre_nms_top_n[k] >= N) else int(pre_nms_top_n[k])
         kmax = max(kmax, K)
     S = B * nl
-    ws = workspace(L_.dtc_rpn_topk_decode_workspace_bytes(lv, nl, B, kmax), dev)
+    ws = workspace(call("dtc_rpn_topk_decode_workspace_bytes", levels=lv, n_levels=nl, batch=B, k_stride=kmax), dev)
     pre_boxes = torch.empty((S, kmax, 4), dtype=torch.float32, device=dev)
     pre_scores = torch.empty((S, kmax), dtype=torch.float32, device=dev)
     pre_counts = torch.empty((S,), dtype=torch.int32, device=dev)
     if im_hw is not None:
         im_hw = torch.as_tensor(im_hw, dtype=torch.float32).to(dev).reshape(B, 2).contiguous()
     with torch.cuda.device(dev):
-        rc = L_.dtc_rpn_topk_decode_sized(lv, nl, B, float(im_h), float(im_w), _ptr(im_hw), float(min_size_scaled),
-                                          ws.data_ptr(), ws.numel(), pre_boxes.data_ptr(), pre_scores.data_ptr(),
-                                          pre_counts.data_ptr(), kmax, stream_ptr(dev))
-    check(rc, "dtc_rpn_topk_decode_sized")
+        call("dtc_rpn_topk_decode_sized", levels=lv, n_levels=nl, batch=B, im_h=im_h, im_w=im_w, im_hw=im_hw,
+             min_size_scaled=min_size_scaled, workspace=ws, workspace_bytes=ws.numel(), out_boxes=pre_boxes, out_scores=pre_scores,
+             out_counts=pre_counts, k_stride=kmax)
     if nms_thresh <= 0:                                   # generate_proposals.py:114
         return (pre_boxes.view(B, nl, kmax, 4), pre_scores.view(B, nl, kmax), pre_counts.view(B, nl),
                 pre_boxes, pre_scores, pre_counts)
@@ -435,22 +493,46 @@ def generate_proposals(cls_probs, bbox_preds, anchors, feat_strides, im_h, im_w,
     out_boxes = torch.empty((S, P, 4), dtype=torch.float32, device=dev)
     out_scores = torch.empty((S, P), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = L_.dtc_gather_kept(pre_boxes.data_ptr(), pre_scores.data_ptr(), S, kmax, keep.data_ptr(), kcnt.data_ptr(),
-                                P, out_boxes.data_ptr(), out_scores.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_gather_kept")
+        call("dtc_gather_kept", sorted_boxes=pre_boxes, sorted_scores=pre_scores, n_seg=S, k_stride=kmax, keep=keep, keep_count=kcnt,
+             keep_stride=P, out_boxes=out_boxes, out_scores=out_scores)
     del alive
     return (out_boxes.view(B, nl, P, 4), out_scores.view(B, nl, P), kcnt.view(B, nl), pre_boxes, pre_scores, pre_counts)
 
 
 def collect_outputs(B, T, n_levels, dev, scores=True):
-    """The output set of dtc_fpn_collect_distribute / _kept / dtc_prepare_proposals for B images x T roi rows, in the entry points'
-    argument order: rois5 [B,T,5], roi_scores [B,T] (None without scores), roi_levels [B,T], n_out [B], rois_by_level [B,T,4],
-    level_counts [B,n_levels], idx_restore [B,T], roi_order [B,T], roi_desc [B,T,8]."""
+    """The output set of dtc_fpn_collect_distribute / _kept / dtc_prepare_proposals for B images x T roi rows, under the entry points'
+    parameter names and in their order (call(entry, ..., **outputs)): rois5 [B,T,5], roi_scores [B,T] (None without scores),
+    roi_levels [B,T], n_out [B], rois_by_level [B,T,4], level_counts [B,n_levels], idx_restore [B,T], roi_order [B,T], roi_desc [B,T,8]."""
     f32, i32 = torch.float32, torch.int32
     e = lambda *shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
     return dict(rois5=e(B, T, 5), roi_scores=e(B, T) if scores else None, roi_levels=e(B, T, dtype=i32), n_out=e(B, dtype=i32),
                 rois_by_level=e(B, T, 4), level_counts=e(B, n_levels, dtype=i32), idx_restore=e(B, T, dtype=i32),
                 roi_order=e(B, T, dtype=i32), roi_desc=e(B, T, 8))
+
+
+def det_outputs(B, D, dev, scaled=True):
+    """The output set of the detection entries for B images x D rows, under dtc_postprocess_detections_ex2's parameter names and in
+    their order: dets [B,D,6], det_roi [B,D], det_rois_scaled [B,D,4] (None without `scaled`: decoded boxes), det_count [B]."""
+    z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+    return dict(dets=z(B, D, 6), det_roi=z(B, D, dtype=torch.int32), det_rois_scaled=z(B, D, 4) if scaled else None,
+                det_count=torch.empty((B,), dtype=torch.int32, device=dev))
+
+
+def paste_outputs(B, D, crop_cols, dev):
+    """The output set of dtc_mask_paste under its parameter names and in their order: crops uint8 [B,crop_cols], mask_boxes /
+    mask_rects int32 [B,D,4], mask_offsets int64 [B,D], mask_bytes int64 [B]."""
+    z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+    return dict(crops=torch.empty((B, crop_cols), dtype=torch.uint8, device=dev), mask_boxes=z(B, D, 4), mask_rects=z(B, D, 4),
+                mask_offsets=z(B, D, dtype=torch.int64), mask_bytes=z(B, dtype=torch.int64))
+
+
+def rle_outputs(B, D, runs_stride, str_stride, dev, zero_str=False):
+    """The output set of dtc_mask_rle under its parameter names and in their order: rle_counts [B,D,runs_stride], rle_n_runs [B,D],
+    rle_str uint8 [B,D,str_stride] (zero_str: cleared, for a path that reads it between steps), rle_str_len [B,D]."""
+    z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+    return dict(rle_counts=torch.empty((B, D, runs_stride), dtype=torch.int32, device=dev), rle_n_runs=z(B, D),
+                rle_str=(torch.zeros if zero_str else torch.empty)((B, D, str_stride), dtype=torch.uint8, device=dev),
+                rle_str_len=z(B, D))
 
 
 def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max=5, inputs_sorted=False):
@@ -466,13 +548,8 @@ def fpn_collect_distribute(boxes, scores, counts, post_nms_top_n, k_min=2, k_max
         scores = scores.contiguous()
     counts = counts.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
-        rc = lib().dtc_fpn_collect_distribute(boxes.data_ptr(), _ptr(scores), counts.data_ptr(), B, Lin, P, T, k_min,
-                                              k_max, out["rois5"].data_ptr(), _ptr(out["roi_scores"]),
-                                              out["roi_levels"].data_ptr(), out["n_out"].data_ptr(),
-                                              out["rois_by_level"].data_ptr(), out["level_counts"].data_ptr(),
-                                              out["idx_restore"].data_ptr(), out["roi_order"].data_ptr(),
-                                              out["roi_desc"].data_ptr(), 1 if inputs_sorted else 0, stream_ptr(dev))
-    check(rc, "dtc_fpn_collect_distribute")
+        call("dtc_fpn_collect_distribute", in_boxes=boxes, in_scores=scores, in_counts=counts, batch=B, n_in_levels=Lin, in_stride=P,
+             post_nms_top_n=T, k_min=k_min, k_max=k_max, inputs_sorted=bool(inputs_sorted), **out)
     return out
 
 
@@ -494,16 +571,13 @@ def prepare_proposals(boxes, counts, im_scale, dedup_scale=0.0625, k_min=2, k_ma
         out["src_index"] = torch.empty((B, T), dtype=i32, device=dev)
     counts = counts.to(i32).contiguous()
     im_scale = torch.as_tensor(im_scale, dtype=f32).to(dev).reshape(B).contiguous()
-    L = lib()
     if ws is None:
-        ws = workspace(L.dtc_prepare_proposals_workspace_bytes(B, T), dev)
+        ws = workspace(call("dtc_prepare_proposals_workspace_bytes", batch=B, max_out=T), dev)
+    outputs = dict({"src_index": None}, **out)               # a given `out` may lack src_index and may carry collect's roi_scores
+    outputs.pop("roi_scores", None)
     with torch.cuda.device(dev):
-        rc = L.dtc_prepare_proposals(boxes.data_ptr(), counts.data_ptr(), im_scale.data_ptr(), B, N, float(dedup_scale), k_min, k_max,
-                                     T, ws.data_ptr(), ws.numel(), out["rois5"].data_ptr(), out["roi_levels"].data_ptr(),
-                                     out["n_out"].data_ptr(), out["rois_by_level"].data_ptr(), out["level_counts"].data_ptr(),
-                                     out["idx_restore"].data_ptr(), out["roi_order"].data_ptr(), out["roi_desc"].data_ptr(),
-                                     _ptr(out.get("src_index")), stream_ptr(dev))
-    check(rc, "dtc_prepare_proposals")
+        call("dtc_prepare_proposals", boxes=boxes, counts=counts, im_scale=im_scale, batch=B, in_stride=N, dedup_scale=dedup_scale,
+             k_min=k_min, k_max=k_max, max_out=T, workspace=ws, workspace_bytes=ws.numel(), **outputs)
     return out
 
 
@@ -512,7 +586,7 @@ def det_workspace_bytes(batch, max_rois, n_cls, opt=None, bbox_vote_method='ID',
     given, a VoteScoring)"""
     if scoring is None:
         scoring = vote_scoring(bbox_vote_method)
-    need = lib().dtc_postprocess_detections_ex2_workspace_bytes(int(batch), int(max_rois), int(n_cls), opt, scoring)
+    need = call("dtc_postprocess_detections_ex2_workspace_bytes", batch=batch, max_rois=max_rois, n_cls=n_cls, opt=opt, scoring=scoring)
     if need == 0:
         raise ValueError("invalid detection post-processing shape or options")
     return need
@@ -531,18 +605,14 @@ def _postprocess(scores, n_rois, rois5, deltas, decoded, sf, im_size, logits, we
     need = det_workspace_bytes(B, R, ncls, opt, scoring=scoring)
     if ws is None or ws.numel() < need:
         ws = workspace(need, dev)
-    dets = torch.zeros((B, max_out, 6), dtype=torch.float32, device=dev)
-    det_roi = torch.zeros((B, max_out), dtype=torch.int32, device=dev)
-    det_scaled = torch.zeros((B, max_out, 4), dtype=torch.float32, device=dev) if decoded is None else None
-    det_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    out = det_outputs(B, max_out, dev, scaled=decoded is None)
+    wx, wy, ww, wh = weights
     with torch.cuda.device(dev):
-        rc = lib().dtc_postprocess_detections_ex2(_ptr(rois5), _ptr(n_rois), scores.data_ptr(), 1 if logits else 0, _ptr(deltas),
-                                                  _ptr(decoded), _ptr(sf), _ptr(im_size), B, R, ncls, *[float(w) for w in weights],
-                                                  float(score_thresh), float(nms_thresh), int(max_det), opt, scoring, ws.data_ptr(),
-                                                  ws.numel(), dets.data_ptr(), det_roi.data_ptr(), _ptr(det_scaled),
-                                                  det_count.data_ptr(), int(max_out), None, stream_ptr(dev))
-    check(rc, "dtc_postprocess_detections_ex2")
-    return dets, det_roi, det_scaled, det_count
+        call("dtc_postprocess_detections_ex2", rois5=rois5, n_rois=n_rois, cls_score=scores, scores_are_logits=bool(logits),
+             bbox_pred=deltas, decoded_boxes=decoded, scaling_factor=sf, im_size=im_size, batch=B, max_rois=R, n_cls=ncls, wx=wx, wy=wy,
+             ww=ww, wh=wh, score_thresh=score_thresh, nms_thresh=nms_thresh, max_det=max_det, opt=opt, scoring=scoring, workspace=ws,
+             workspace_bytes=ws.numel(), max_out=max_out, fpn=None, **out)
+    return tuple(out.values())
 
 
 def postprocess_detections(rois5, n_rois, cls_score, bbox_pred, scaling_factor, im_size, weights=(10., 10., 5., 5.),
@@ -581,19 +651,12 @@ def mask_paste(masks, dets, det_count, im_size, M, per_image_capacity, mask_inde
     masks, dets = masks.contiguous(), dets.contiguous()
     B, D = dets.shape[0], dets.shape[1]
     cap = int(per_image_capacity)
-    out = dict(crops=torch.empty((B, max(cap, 1)), dtype=torch.uint8, device=dev),
-               boxes=torch.zeros((B, D, 4), dtype=torch.int32, device=dev),
-               rects=torch.zeros((B, D, 4), dtype=torch.int32, device=dev),
-               offsets=torch.zeros((B, D), dtype=torch.int64, device=dev),
-               bytes=torch.zeros((B,), dtype=torch.int64, device=dev))
+    out = paste_outputs(B, D, max(cap, 1), dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_mask_paste(masks.data_ptr(), _ptr(mask_index), masks.shape[1], int(M), dets.data_ptr(),
-                                  det_count.data_ptr(), im_size.to(torch.float32).contiguous().data_ptr(), B, D,
-                                  float(thresh), 1 if cls_specific else 0, out["crops"].data_ptr(), cap,
-                                  out["boxes"].data_ptr(), out["rects"].data_ptr(), out["offsets"].data_ptr(),
-                                  out["bytes"].data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_mask_paste")
-    return out
+        call("dtc_mask_paste", masks=masks, mask_index=mask_index, n_cls=masks.shape[1], M=M, dets=dets, det_count=det_count,
+             im_size=im_size.to(torch.float32).contiguous(), batch=B, max_out=D, thresh_binarize=thresh,
+             cls_specific_mask=bool(cls_specific), per_image_capacity=cap, **out)
+    return {k.replace("mask_", ""): v for k, v in out.items()}
 
 
 def mask_rle(paste, det_count, im_size, runs_stride=4096, str_stride=8192):
@@ -602,17 +665,11 @@ def mask_rle(paste, det_count, im_size, runs_stride=4096, str_stride=8192):
     crops, rects, offs = paste["crops"], paste["rects"], paste["offsets"]
     dev = _require_cuda(crops, rects, offs, det_count, im_size)
     B, D = rects.shape[0], rects.shape[1]
-    out = dict(counts=torch.empty((B, D, int(runs_stride)), dtype=torch.int32, device=dev),
-               n_runs=torch.zeros((B, D), dtype=torch.int32, device=dev),
-               str=torch.empty((B, D, int(str_stride)), dtype=torch.uint8, device=dev),
-               str_len=torch.zeros((B, D), dtype=torch.int32, device=dev))
+    out = rle_outputs(B, D, int(runs_stride), int(str_stride), dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_mask_rle(crops.data_ptr(), int(crops.shape[1]), rects.data_ptr(), offs.data_ptr(),
-                                det_count.data_ptr(), im_size.to(torch.float32).contiguous().data_ptr(), B, D,
-                                out["counts"].data_ptr(), int(runs_stride), out["n_runs"].data_ptr(),
-                                out["str"].data_ptr(), int(str_stride), out["str_len"].data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_mask_rle")
-    return out
+        call("dtc_mask_rle", crops=crops, per_image_capacity=crops.shape[1], mask_rects=rects, mask_offsets=offs, det_count=det_count,
+             im_size=im_size.to(torch.float32).contiguous(), batch=B, max_out=D, runs_stride=runs_stride, str_stride=str_stride, **out)
+    return {k.replace("rle_", ""): v for k, v in out.items()}
 
 
 def bbox_overlaps(boxes, query_boxes):
@@ -622,9 +679,8 @@ def bbox_overlaps(boxes, query_boxes):
     n, k = boxes.shape[0], query_boxes.shape[0]
     out = torch.zeros((n, k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_bbox_overlaps(boxes.data_ptr(), n, boxes.shape[1] if n else 4, query_boxes.data_ptr(), k,
-                                     query_boxes.shape[1] if k else 4, out.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_bbox_overlaps")
+        call("dtc_bbox_overlaps", boxes=boxes, n=n, box_cols=boxes.shape[1] if n else 4, query_boxes=query_boxes, k=k,
+             query_cols=query_boxes.shape[1] if k else 4, overlaps=out)
     return out
 
 
@@ -638,9 +694,8 @@ def box_voting(top_dets, all_dets, thresh, scoring_method='ID', beta=1.0):
     out = torch.empty((t, 5), dtype=torch.float32, device=dev)
     nv = torch.zeros((max(t, 1),), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_box_voting_scored(top_dets.data_ptr(), t, all_dets.data_ptr(), a, float(thresh), scoring, out.data_ptr(),
-                                         nv.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_box_voting_scored")
+        call("dtc_box_voting_scored", top_dets=top_dets, n_top=t, all_dets=all_dets, n_all=a, thresh=thresh, scoring=scoring,
+             top_dets_out=out, n_voters=nv)
     return out, nv[:t]
 
 
@@ -655,8 +710,8 @@ def prep_images(images, pixel_means=(122.7717, 115.9465, 102.9801), target_size=
     scales = (C.c_double * B)()
     out_hw = (C.c_int32 * (2 * B))()
     blob_hw = (C.c_int32 * 2)()
-    check(lib().dtc_prep_plan(hs, ws_, B, int(target_size), int(max_size), int(pad_stride), scales, out_hw, blob_hw),
-          "dtc_prep_plan")
+    call("dtc_prep_plan", heights=hs, widths=ws_, batch=B, target_size=target_size, max_size=max_size, pad_stride=pad_stride,
+         im_scales=scales, out_hw=out_hw, blob_hw=blob_hw)
     arr = (Image * B)()
     for k, im in enumerate(ims):
         if im.dtype == torch.uint8:
@@ -671,8 +726,8 @@ def prep_images(images, pixel_means=(122.7717, 115.9465, 102.9801), target_size=
     means = (C.c_double * 3)(*[float(m) for m in pixel_means])
     blob = torch.empty((B, 3, blob_hw[0], blob_hw[1]), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_prep_images(arr, B, means, scales, out_hw, blob.data_ptr(), blob_hw[0], blob_hw[1], stream_ptr(dev))
-    check(rc, "dtc_prep_images")
+        call("dtc_prep_images", images=arr, batch=B, pixel_means=means, im_scales=scales, out_hw=out_hw, blob=blob,
+             blob_h=blob_hw[0], blob_w=blob_hw[1])
     del ims
     return blob, [float(s) for s in scales], [(out_hw[2 * k], out_hw[2 * k + 1]) for k in range(B)]
 
@@ -686,9 +741,8 @@ def soft_nms(dets, sigma, overlap_thresh, score_thresh, method):
     inds = torch.empty((max(n, 1),), dtype=torch.int64, device=dev)
     cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib().dtc_soft_nms(dets.data_ptr(), n, float(sigma), float(overlap_thresh), float(score_thresh), int(method),
-                                out.data_ptr(), inds.data_ptr(), cnt.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_soft_nms")
+        call("dtc_soft_nms", dets=dets, n=n, sigma=sigma, overlap_thresh=overlap_thresh, score_thresh=score_thresh, method=method,
+             dets_out=out, inds_out=inds, n_out=cnt)
     k = int(cnt.item())
     return out[:k], inds[:k]
 
@@ -699,9 +753,8 @@ def bbox_transform(boxes, deltas, weights, clip_to=None):
     boxes, deltas = boxes.contiguous(), deltas.contiguous()
     n, k = deltas.shape[0], deltas.shape[1] // 4
     out = torch.empty_like(deltas)
+    (wx, wy, ww, wh), (im_h, im_w) = weights, clip_to if clip_to is not None else (0.0, 0.0)
     with torch.cuda.device(dev):
-        rc = lib().dtc_bbox_transform(boxes.data_ptr(), deltas.data_ptr(), n, k, *[float(w) for w in weights],
-                                      1 if clip_to is not None else 0, float(clip_to[0]) if clip_to is not None else 0.0,
-                                      float(clip_to[1]) if clip_to is not None else 0.0, out.data_ptr(), stream_ptr(dev))
-    check(rc, "dtc_bbox_transform")
+        call("dtc_bbox_transform", boxes=boxes, deltas=deltas, n=n, n_cls=k, wx=wx, wy=wy, ww=ww, wh=wh, do_clip=clip_to is not None,
+             im_h=im_h, im_w=im_w, out=out)
     return out

@@ -9,7 +9,8 @@ import os
 import torch
 
 from . import build as _build
-from .hip import _ptr, _require_cuda, check, stream_ptr
+from . import hip
+from .hip import _require_cuda
 
 LIB_PATH = os.environ.get("DETECTORCH_TRAIN_HIP_LIB") or _build.TRAIN_LIB
 
@@ -31,6 +32,14 @@ def train_params(rois_per_image=512, fg_fraction=0.25, fg_thresh=0.5, bg_thresh_
                        (C.c_float * 4)(*[float(w) for w in reg_weights]))
 
 
+# include/detectorch_train_hip.h, one row per exported function (the format of hip._SIGNATURES)
+SIGNATURES = hip.signatures("""
+str dtc_train_target_arch()
+status dtc_fast_rcnn_targets(gt_boxes gt_classes gt_is_crowd gt_counts proposals proposal_counts im_scale rand_keys batch:i
+    gt_stride:i proposal_stride:i params:TrainParams rois5 labels bbox_targets5 bbox_targets bbox_inside_weights
+    bbox_outside_weights keep_inds n_fg n_rois max_overlaps max_classes stream)
+""", {"TrainParams": TrainParams})
+
 _lib = None
 
 
@@ -44,13 +53,8 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("detectorch_amd: %s is missing. Build it with `python -m detectorch_amd.build` (hipcc, gfx950). "
                            "There is no CPU/PyTorch fallback for the training targets." % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    p, i = C.c_void_p, C.c_int
-    L.dtc_train_target_arch.restype = C.c_char_p
-    L.dtc_fast_rcnn_targets.argtypes = [p, p, p, p, p, p, p, p, i, i, i, C.POINTER(TrainParams), p, p, p, p, p, p, p, p, p, p, p, p]
-    L.dtc_fast_rcnn_targets.restype = i
-    _lib = L
-    return L
+    _lib = hip.typed(C.CDLL(LIB_PATH), SIGNATURES)
+    return _lib
 
 
 def targets_outputs(B, n_cand, params, dev, expanded=True, assignment=False):
@@ -87,11 +91,8 @@ def fast_rcnn_targets(gt_boxes, gt_classes, gt_is_crowd, gt_counts, proposals, p
     if out is None:
         out = targets_outputs(B, G + P, params, dev, expanded, assignment)
     with torch.cuda.device(dev):
-        rc = lib().dtc_fast_rcnn_targets(
-            _ptr(gt_boxes), _ptr(gt_classes), _ptr(gt_is_crowd), _ptr(gt_counts), _ptr(proposals), _ptr(proposal_counts),
-            _ptr(im_scale), _ptr(rand_keys), B, G, P, C.byref(params), _ptr(out["rois5"]), _ptr(out["labels"]),
-            _ptr(out["bbox_targets5"]), _ptr(out["bbox_targets"]), _ptr(out["bbox_inside_weights"]),
-            _ptr(out["bbox_outside_weights"]), _ptr(out["keep_inds"]), _ptr(out["n_fg"]), _ptr(out["n_rois"]),
-            _ptr(out["max_overlaps"]), _ptr(out["max_classes"]), stream_ptr(dev))
-    check(rc, "dtc_fast_rcnn_targets")
+        hip.invoke(lib(), SIGNATURES, "dtc_fast_rcnn_targets", dict(
+            gt_boxes=gt_boxes, gt_classes=gt_classes, gt_is_crowd=gt_is_crowd, gt_counts=gt_counts, proposals=proposals,
+            proposal_counts=proposal_counts, im_scale=im_scale, rand_keys=rand_keys, batch=B, gt_stride=G, proposal_stride=P,
+            params=params, **out))
     return out

@@ -397,10 +397,8 @@ class detector(nn.Module):
             odt = self.head_dtype or torch.float32
             roi_features = torch.empty((T, img_features[0].shape[1], self.roi_height, self.roi_width), dtype=odt, device=image.device)
             lvs, ch, dt = hip.make_levels(list(img_features), self.roi_spatial_scale)
-            hip.check(hip.lib().dtc_roi_align_forward_packed(lvs, len(self.roi_spatial_scale), ch, hip._dtype_code(dt),
-                                                             fused["roi_desc"].data_ptr(), T, self.roi_height, self.roi_width,
-                                                             self.roi_sampling_ratio, roi_features.data_ptr(), hip._dtype_code(odt),
-                                                             hip.stream_ptr(image.device)), "roi_align(packed)")
+            hip.roi_align_packed(lvs, ch, dt, fused["roi_desc"], T, self.roi_height, self.roi_width, self.roi_sampling_ratio,
+                                 roi_features)
             n = int(fused["n_out"][0].item())
             roi_features = roi_features[:n]
             rois = fused["rois5"][0, :n, 1:]

@@ -93,7 +93,6 @@ class RegionPath(_GraphStep):
 
     def _alloc(self, ra_workspace):
         B, dev, f32, i32 = self.B, self.dev, torch.float32, torch.int32
-        L = hip.lib()
         e = lambda *shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
         zeros = lambda *shape, dtype=f32: torch.zeros(shape, dtype=dtype, device=dev)
         S, T, D, nl = B * len(self.strides), self.top_n, self.max_out, len(self.roi_scales)
@@ -102,34 +101,34 @@ class RegionPath(_GraphStep):
         self.keep, self.keep_cnt = e(S, self.P, dtype=i32), e(S, dtype=i32)
         # per-level proposals after NMS (generate_proposals.py:119-120), written by the gather launch
         self._prop_boxes, self._prop_scores = zeros(S, self.P, 4), zeros(S, self.P)
-        self.nms_ws = hip.workspace(L.dtc_nms_sorted_workspace_bytes(S, self.kmax), dev)
+        self.nms_ws = hip.workspace(hip.call("dtc_nms_sorted_workspace_bytes", n_seg=S, n_stride=self.kmax), dev)
+        # (each output set is kept twice: as the dict a by-name call takes, and under the attribute names its readers use)
+        self._roi_out = hip.collect_outputs(B, T, nl, dev)
         (self.rois5, self.roi_scores, self.roi_levels, self.n_rois, self.rois_by_level, self.level_counts, self.idx_restore,
-         self.roi_order, self.roi_desc) = hip.collect_outputs(B, T, nl, dev).values()
+         self.roi_order, self.roi_desc) = self._roi_out.values()
         self.box_feats = e(B * T, self.C, self.box_p, self.box_p, dtype=self.feat_dtype)
         # (RoIAlign workspace: the per-RoI records the map-stationary kernel's preparation pass writes, csrc/roi_align_map.hip)
-        ra_ws = lambda rows: hip.workspace(L.dtc_roi_align_workspace_bytes(rows), dev) if ra_workspace else None
+        ra_ws = lambda rows: hip.workspace(hip.call("dtc_roi_align_workspace_bytes", n_rois=rows), dev) if ra_workspace else None
         self.ra_ws = ra_ws(B * T)
-        self.dets, self.det_roi = zeros(B, D, 6), zeros(B, D, dtype=i32)
-        self.det_scaled, self.det_count = zeros(B, D, 4), e(B, dtype=i32)
+        self._det_out = hip.det_outputs(B, D, dev)
+        self.dets, self.det_roi, self.det_scaled, self.det_count = self._det_out.values()
         self.det_ws = hip.workspace(hip.det_workspace_bytes(B, T, self.n_cls, self.det_opt, scoring=self.det_scoring), dev)
         if not self.with_masks:
             return
         # the mask branch's rois / level ids / visiting order: out of the detection launch itself (dtc_fpn_map_out, <= 512 rows), or
         # of a separate mapping launch
+        self._mask_roi_out = hip.collect_outputs(B, D, nl, dev, scores=False)
         (self.m_rois5, _, self.m_levels, self.m_n, self.m_by_level, self.m_level_counts, self.m_restore, self.m_order,
-         self.m_desc) = hip.collect_outputs(B, D, nl, dev, scores=False).values()
-        self.m_map = hip.FpnMapOut(self.m_rois5.data_ptr(), self.m_levels.data_ptr(), self.m_n.data_ptr(), self.m_by_level.data_ptr(),
-                                   self.m_level_counts.data_ptr(), self.m_restore.data_ptr(), self.m_order.data_ptr(),
-                                   self.m_desc.data_ptr(), self.k_min, self.k_max)
+         self.m_desc) = self._mask_roi_out.values()
+        self.m_map = hip.FpnMapOut(k_min=self.k_min, k_max=self.k_max,
+                                   **{k: t.data_ptr() for k, t in self._mask_roi_out.items() if t is not None})
         self.mask_feats = e(B * D, self.C, self.mask_p, self.mask_p, dtype=self.feat_dtype)
         self.m_ra_ws = ra_ws(B * D)
-        self.crops = torch.empty((B, self.crop_capacity), dtype=torch.uint8, device=dev)
-        self.mask_boxes, self.mask_rects = zeros(B, D, 4, dtype=i32), zeros(B, D, 4, dtype=i32)
-        self.mask_offsets, self.mask_bytes = zeros(B, D, dtype=torch.int64), zeros(B, dtype=torch.int64)
+        self._paste_out = hip.paste_outputs(B, D, self.crop_capacity, dev)
+        self.crops, self.mask_boxes, self.mask_rects, self.mask_offsets, self.mask_bytes = self._paste_out.values()
         if self.with_rle:    # COCO RLE of every pasted mask, on the device (dtc_mask_rle): ~100 bytes per mask leave the GPU
-            self.rle_counts = e(B, D, self.rle_runs_stride, dtype=i32)
-            self.rle_n_runs, self.rle_str_len = zeros(B, D, dtype=i32), zeros(B, D, dtype=i32)
-            self.rle_str = zeros(B, D, self.rle_str_stride, dtype=torch.uint8)
+            self._rle_out = hip.rle_outputs(B, D, self.rle_runs_stride, self.rle_str_stride, dev, zero_str=True)
+            self.rle_counts, self.rle_n_runs, self.rle_str, self.rle_str_len = self._rle_out.values()
 
     # ---- binding.  The three stages can be bound / launched one by one by a model that runs its head GEMMs / convs in between
     # (detector.forward_batched):  launch_proposals -> box head -> launch_detections -> mask head -> launch_masks ------------------
@@ -144,7 +143,7 @@ class RegionPath(_GraphStep):
         n = len(self.strides)
         self.rpn_lv, self._alive = hip.make_rpn_levels(rpn_cls, rpn_bbox, self.anchors, self.strides, [self.pre] * n,
                                                        scores_are_logits=scores_are_logits)
-        need = hip.lib().dtc_rpn_topk_decode_workspace_bytes(self.rpn_lv, n, self.B, self.kmax)
+        need = hip.call("dtc_rpn_topk_decode_workspace_bytes", levels=self.rpn_lv, n_levels=n, batch=self.B, k_stride=self.kmax)
         if getattr(self, "rpn_ws", None) is None or self.rpn_ws.numel() < need:
             self.rpn_ws = hip.workspace(need, self.dev)
         self._bind_feats(feats)
@@ -174,7 +173,9 @@ class RegionPath(_GraphStep):
         self.prop_im_scale = _device_input(im_scale, torch.float32, (B,), dev)
         self.prop_dedup = float(dedup_scale)
         self.prop_src = torch.zeros((B, self.top_n), dtype=torch.int32, device=dev)
-        self.prep_ws = hip.workspace(hip.lib().dtc_prepare_proposals_workspace_bytes(B, self.top_n), dev)
+        self._prep_out = dict(self._roi_out, src_index=self.prop_src)             # dtc_prepare_proposals writes no roi_scores
+        del self._prep_out["roi_scores"]
+        self.prep_ws = hip.workspace(hip.call("dtc_prepare_proposals_workspace_bytes", batch=B, max_out=self.top_n), dev)
 
     def bind_heads(self, cls_score, bbox_pred, scaling_factor, im_size):
         self.cls_score, self.bbox_pred = cls_score, bbox_pred
@@ -188,92 +189,75 @@ class RegionPath(_GraphStep):
 
     # ---- one method per launch (st: the HIP stream handle) -----------------------------------------------------------------
     def _rpn_topk_decode(self, st):
-        hip.check(hip.lib().dtc_rpn_topk_decode_sized(
-            self.rpn_lv, len(self.strides), self.B, float(self.pad_h), float(self.pad_w), hip._ptr(self.rpn_im_hw), 0.0,
-            self.rpn_ws.data_ptr(), self.rpn_ws.numel(), self.pre_boxes.data_ptr(), self.pre_scores.data_ptr(),
-            self.pre_counts.data_ptr(), self.kmax, st), "rpn_topk_decode")
+        hip.call("dtc_rpn_topk_decode_sized", "rpn_topk_decode", levels=self.rpn_lv, n_levels=len(self.strides), batch=self.B,
+                 im_h=self.pad_h, im_w=self.pad_w, im_hw=self.rpn_im_hw, min_size_scaled=0.0, workspace=self.rpn_ws,
+                 workspace_bytes=self.rpn_ws.numel(), out_boxes=self.pre_boxes, out_scores=self.pre_scores, out_counts=self.pre_counts,
+                 k_stride=self.kmax, stream=st)
 
     def _nms_sorted(self, st):
-        hip.check(hip.lib().dtc_nms_sorted(
-            self.pre_boxes.data_ptr(), self.pre_counts.data_ptr(), self.B * len(self.strides), self.kmax, self.rpn_thresh, self.P,
-            self.nms_ws.data_ptr(), self.nms_ws.numel(), self.keep.data_ptr(), self.P, self.keep_cnt.data_ptr(), st), "nms_sorted")
+        hip.call("dtc_nms_sorted", "nms_sorted", boxes=self.pre_boxes, counts=self.pre_counts, n_seg=self.B * len(self.strides),
+                 n_stride=self.kmax, thresh=self.rpn_thresh, max_keep=self.P, workspace=self.nms_ws, workspace_bytes=self.nms_ws.numel(),
+                 keep=self.keep, keep_stride=self.P, keep_count=self.keep_cnt, stream=st)
 
     def _gather_kept(self, st=None):
-        st = st or hip.stream_ptr(self.dev)
-        hip.check(hip.lib().dtc_gather_kept(
-            self.pre_boxes.data_ptr(), self.pre_scores.data_ptr(), self.B * len(self.strides), self.kmax, self.keep.data_ptr(),
-            self.keep_cnt.data_ptr(), self.P, self._prop_boxes.data_ptr(), self._prop_scores.data_ptr(), st), "gather_kept")
+        hip.call("dtc_gather_kept", "gather_kept", sorted_boxes=self.pre_boxes, sorted_scores=self.pre_scores,
+                 n_seg=self.B * len(self.strides), k_stride=self.kmax, keep=self.keep, keep_count=self.keep_cnt, keep_stride=self.P,
+                 out_boxes=self._prop_boxes, out_scores=self._prop_scores, stream=st or hip.stream_ptr(self.dev))
 
     def _collect_kept(self, st):
-        hip.check(hip.lib().dtc_fpn_collect_distribute_kept(
-            self.pre_boxes.data_ptr(), self.pre_scores.data_ptr(), self.kmax, self.keep.data_ptr(), self.keep_cnt.data_ptr(), self.P,
-            self.B, len(self.strides), self.top_n, self.k_min, self.k_max, self.rois5.data_ptr(), self.roi_scores.data_ptr(),
-            self.roi_levels.data_ptr(), self.n_rois.data_ptr(), self.rois_by_level.data_ptr(), self.level_counts.data_ptr(),
-            self.idx_restore.data_ptr(), self.roi_order.data_ptr(), self.roi_desc.data_ptr(), st), "fpn_collect_kept")
+        hip.call("dtc_fpn_collect_distribute_kept", "fpn_collect_kept", sorted_boxes=self.pre_boxes, sorted_scores=self.pre_scores,
+                 k_stride=self.kmax, keep=self.keep, keep_count=self.keep_cnt, keep_stride=self.P, batch=self.B,
+                 n_in_levels=len(self.strides), post_nms_top_n=self.top_n, k_min=self.k_min, k_max=self.k_max, stream=st,
+                 **self._roi_out)
+
+    def _collect_distribute(self, what, st, outputs, **lists):
+        hip.call("dtc_fpn_collect_distribute", what, batch=self.B, k_min=self.k_min, k_max=self.k_max, stream=st, **lists, **outputs)
 
     def _collect(self, st):
         """the gathered per-level lists (one per image and level, already in score order) -> rois5 (b, box), level ids, the RoIAlign
         visiting order; k_min == k_max -> level 0"""
-        hip.check(hip.lib().dtc_fpn_collect_distribute(
-            self._prop_boxes.data_ptr(), self._prop_scores.data_ptr(), self.keep_cnt.data_ptr(), self.B, len(self.strides), self.P,
-            self.top_n, self.k_min, self.k_max, self.rois5.data_ptr(), self.roi_scores.data_ptr(), self.roi_levels.data_ptr(),
-            self.n_rois.data_ptr(), self.rois_by_level.data_ptr(), self.level_counts.data_ptr(), self.idx_restore.data_ptr(),
-            self.roi_order.data_ptr(), self.roi_desc.data_ptr(), 1, st), "fpn_collect")
+        self._collect_distribute("fpn_collect", st, self._roi_out, in_boxes=self._prop_boxes, in_scores=self._prop_scores,
+                                 in_counts=self.keep_cnt, n_in_levels=len(self.strides), in_stride=self.P, post_nms_top_n=self.top_n,
+                                 inputs_sorted=1)
 
     def _prepare_proposals(self, st):
-        hip.check(hip.lib().dtc_prepare_proposals(
-            self.prop_in.data_ptr(), self.prop_in_counts.data_ptr(), self.prop_im_scale.data_ptr(), self.B, self.prop_in.shape[1],
-            self.prop_dedup, self.k_min, self.k_max, self.top_n, self.prep_ws.data_ptr(), self.prep_ws.numel(), self.rois5.data_ptr(),
-            self.roi_levels.data_ptr(), self.n_rois.data_ptr(), self.rois_by_level.data_ptr(), self.level_counts.data_ptr(),
-            self.idx_restore.data_ptr(), self.roi_order.data_ptr(), self.roi_desc.data_ptr(), self.prop_src.data_ptr(), st),
-            "prepare_proposals")
-
-    def _roi_align(self, desc, rows, pooled, out, ws, st, what):
-        L, n = hip.lib(), len(self.roi_scales)
-        if ws is None:
-            hip.check(L.dtc_roi_align_forward_packed(self.feat_lv, n, self.C, self.feat_code, desc.data_ptr(), rows, pooled, pooled,
-                                                     self.sr, out.data_ptr(), self.out_code, st), what)
-        else:
-            hip.check(L.dtc_roi_align_forward_packed_ws(self.feat_lv, n, self.C, self.feat_code, desc.data_ptr(), rows, pooled, pooled,
-                                                        self.sr, out.data_ptr(), self.out_code, ws.data_ptr(), ws.numel(), st), what)
+        hip.call("dtc_prepare_proposals", "prepare_proposals", boxes=self.prop_in, counts=self.prop_in_counts,
+                 im_scale=self.prop_im_scale, batch=self.B, in_stride=self.prop_in.shape[1], dedup_scale=self.prop_dedup,
+                 k_min=self.k_min, k_max=self.k_max, max_out=self.top_n, workspace=self.prep_ws, workspace_bytes=self.prep_ws.numel(),
+                 stream=st, **self._prep_out)
 
     def _roi_align_box(self, st=None):
-        self._roi_align(self.roi_desc, self.B * self.top_n, self.box_p, self.box_feats, self.ra_ws,
-                        st or hip.stream_ptr(self.dev), "roi_align(box)")
+        hip.roi_align_packed(self.feat_lv, self.C, self.feats[0].dtype, self.roi_desc, self.B * self.top_n, self.box_p, self.box_p,
+                             self.sr, self.box_feats, self.ra_ws, st, "roi_align(box)")
 
     def _roi_align_mask(self, st=None):
-        self._roi_align(self.m_desc, self.B * self.max_out, self.mask_p, self.mask_feats, self.m_ra_ws,
-                        st or hip.stream_ptr(self.dev), "roi_align(mask)")
+        hip.roi_align_packed(self.feat_lv, self.C, self.feats[0].dtype, self.m_desc, self.B * self.max_out, self.mask_p, self.mask_p,
+                             self.sr, self.mask_feats, self.m_ra_ws, st, "roi_align(mask)")
 
     def _postprocess_detections(self, st):
         # one entry for both forms (dtc_postprocess_detections_ex2): with the fused mask-branch mapping (fpn != NULL), or without
-        hip.check(hip.lib().dtc_postprocess_detections_ex2(
-            self.rois5.data_ptr(), self.n_rois.data_ptr(), self.cls_score.data_ptr(), 1 if self.cls_logits else 0,
-            self.bbox_pred.data_ptr(), None, self.sf.data_ptr(), self.im_size.data_ptr(), self.B, self.top_n, self.n_cls,
-            10.0, 10.0, 5.0, 5.0, 0.05, 0.5, self.max_det, self.det_opt, self.det_scoring, self.det_ws.data_ptr(),
-            self.det_ws.numel(), self.dets.data_ptr(), self.det_roi.data_ptr(), self.det_scaled.data_ptr(),
-            self.det_count.data_ptr(), self.max_out, self.m_map if self.fused_mask_map else None, st), "postprocess_detections_ex2")
+        hip.call("dtc_postprocess_detections_ex2", "postprocess_detections_ex2", rois5=self.rois5, n_rois=self.n_rois,
+                 cls_score=self.cls_score, scores_are_logits=bool(self.cls_logits), bbox_pred=self.bbox_pred, decoded_boxes=None,
+                 scaling_factor=self.sf, im_size=self.im_size, batch=self.B, max_rois=self.top_n, n_cls=self.n_cls, wx=10.0, wy=10.0,
+                 ww=5.0, wh=5.0, score_thresh=0.05, nms_thresh=0.5, max_det=self.max_det, opt=self.det_opt, scoring=self.det_scoring,
+                 workspace=self.det_ws, workspace_bytes=self.det_ws.numel(), max_out=self.max_out,
+                 fpn=self.m_map if self.fused_mask_map else None, stream=st, **self._det_out)
 
     def _map_mask_levels(self, st):
         """mask branch: level ids of the (scaled) detection boxes, multilevel_rois.py:19-39, as a launch of its own"""
-        D = self.max_out
-        hip.check(hip.lib().dtc_fpn_collect_distribute(
-            self.det_scaled.data_ptr(), None, self.det_count.data_ptr(), self.B, 1, D, D, self.k_min, self.k_max,
-            self.m_rois5.data_ptr(), None, self.m_levels.data_ptr(), self.m_n.data_ptr(), self.m_by_level.data_ptr(),
-            self.m_level_counts.data_ptr(), self.m_restore.data_ptr(), self.m_order.data_ptr(), self.m_desc.data_ptr(), 0, st),
-            "fpn_map_levels")
+        self._collect_distribute("fpn_map_levels", st, self._mask_roi_out, in_boxes=self.det_scaled, in_scores=None,
+                                 in_counts=self.det_count, n_in_levels=1, in_stride=self.max_out, post_nms_top_n=self.max_out,
+                                 inputs_sorted=0)
 
     def _mask_paste(self, st):
-        hip.check(hip.lib().dtc_mask_paste(
-            self.masks.data_ptr(), None, self.n_cls, self.M, self.dets.data_ptr(), self.det_count.data_ptr(), self.im_size.data_ptr(),
-            self.B, self.max_out, 0.5, 1, self.crops.data_ptr(), self.crop_capacity, self.mask_boxes.data_ptr(),
-            self.mask_rects.data_ptr(), self.mask_offsets.data_ptr(), self.mask_bytes.data_ptr(), st), "mask_paste")
+        hip.call("dtc_mask_paste", "mask_paste", masks=self.masks, mask_index=None, n_cls=self.n_cls, M=self.M, dets=self.dets,
+                 det_count=self.det_count, im_size=self.im_size, batch=self.B, max_out=self.max_out, thresh_binarize=0.5,
+                 cls_specific_mask=1, per_image_capacity=self.crop_capacity, stream=st, **self._paste_out)
 
     def _mask_rle(self, st):
-        hip.check(hip.lib().dtc_mask_rle(
-            self.crops.data_ptr(), self.crop_capacity, self.mask_rects.data_ptr(), self.mask_offsets.data_ptr(),
-            self.det_count.data_ptr(), self.im_size.data_ptr(), self.B, self.max_out, self.rle_counts.data_ptr(), self.rle_runs_stride,
-            self.rle_n_runs.data_ptr(), self.rle_str.data_ptr(), self.rle_str_stride, self.rle_str_len.data_ptr(), st), "mask_rle")
+        hip.call("dtc_mask_rle", "mask_rle", crops=self.crops, per_image_capacity=self.crop_capacity, mask_rects=self.mask_rects,
+                 mask_offsets=self.mask_offsets, det_count=self.det_count, im_size=self.im_size, batch=self.B, max_out=self.max_out,
+                 runs_stride=self.rle_runs_stride, str_stride=self.rle_str_stride, stream=st, **self._rle_out)
 
     # ---- one pass of the hot path over the bound batch: three stages.  A stage called with a stream handle launches on it;
     # without, on the device's current stream ------------------------------------------------------------------------------------

@@ -75,14 +75,14 @@ def main():
         scoring = hip.vote_scoring(kw.pop("bbox_vote_method", "ID"))
         opt = hip.det_options(**kw)
         ws = hip.workspace(hip.det_workspace_bytes(B, R, ncls, opt, scoring=scoring), dev)
-        out = [torch.zeros((B, 128, 6), device=dev), torch.zeros((B, 128), dtype=torch.int32, device=dev),
-               torch.zeros((B, 128, 4), device=dev), torch.zeros((B,), dtype=torch.int32, device=dev)]
-        L, st = hip.lib(), hip.stream_ptr(dev)
+        out = hip.det_outputs(B, 128, dev)
+        st = hip.stream_ptr(dev)
 
         def launch():
-            hip.check(L.dtc_postprocess_detections_ex2(rois.data_ptr(), None, logits.data_ptr(), 1, bbox.data_ptr(), None, sf.data_ptr(),
-                                                       im.data_ptr(), B, R, ncls, 10., 10., 5., 5., .05, .5, 100, opt, scoring,
-                                                       ws.data_ptr(), ws.numel(), *[t.data_ptr() for t in out], 128, None, st), name)
+            hip.call("dtc_postprocess_detections_ex2", name, rois5=rois, n_rois=None, cls_score=logits, scores_are_logits=1, bbox_pred=bbox,
+                     decoded_boxes=None, scaling_factor=sf, im_size=im, batch=B, max_rois=R, n_cls=ncls, wx=10., wy=10., ww=5., wh=5.,
+                     score_thresh=.05, nms_thresh=.5, max_det=100, opt=opt, scoring=scoring, workspace=ws, workspace_bytes=ws.numel(),
+                     max_out=128, fpn=None, stream=st, **out)
         for _ in range(a.warmup):
             launch()
         torch.cuda.synchronize()
@@ -95,7 +95,7 @@ def main():
             e1.synchronize()
             ts.append(e0.elapsed_time(e1) * 1e3)
         print(json.dumps(dict(mode=name, median_us=round(statistics.median(ts), 1), min_us=round(min(ts), 1), iters=a.iters, batch=B,
-                              rois=R, classes=ncls, dets_per_image=out[3].tolist(), **seg)), flush=True)
+                              rois=R, classes=ncls, dets_per_image=out["det_count"].tolist(), **seg)), flush=True)
     # host-loop baseline: decoded boxes of the same images, the old per-class loop (one single-segment launch + sync per class)
     n = min(a.host_images, B)
     dec = [hip.bbox_transform(rois[b, :, 1:] / sf[b], bbox[b], (10., 10., 5., 5.), clip_to=(float(im[b, 0]), float(im[b, 1])))
