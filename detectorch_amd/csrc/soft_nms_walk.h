@@ -20,10 +20,14 @@ __device__ __forceinline__ int soft_nms_walk(float* X1, float* Y1, float* X2, fl
   int N = n;
   for (int i = 0; i < N; i++) {
     // ---- argmax over [i, N): first maximum in scan order (strict <)  :128-132
+    // NaN scores as the reference's `maxscore < boxes[pos, 4]` treats them: the scan starts from row i and a compare with a NaN is
+    // false either way, so a NaN at row i stays the pick and a NaN anywhere else is never picked.  Here: NaN candidates are skipped
+    // (a lane without candidates keeps the sentinel, so bs is never NaN in the butterfly), and a NaN at row i overrides the result.
+    const float si = S[i];
     float bs = -INFINITY; int bp = 0x7fffffff;
     for (int pos = i + lane; pos < N; pos += 64) {
       const float s = S[pos];
-      if (bp == 0x7fffffff || s > bs) { bs = s; bp = pos; }   // within a lane positions ascend: keep the first max
+      if (s == s && (bp == 0x7fffffff || s > bs)) { bs = s; bp = pos; }   // within a lane positions ascend: keep the first max
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -32,7 +36,7 @@ __device__ __forceinline__ int soft_nms_walk(float* X1, float* Y1, float* X2, fl
       const bool take = (op != 0x7fffffff) && (bp == 0x7fffffff || os > bs || (os == bs && op < bp));
       if (take) { bs = os; bp = op; }
     }
-    const int maxpos = bp;
+    const int maxpos = si == si ? bp : i;
     // ---- swap rows i and maxpos  :135-148
     if (lane == 0 && maxpos != i) {
       float t;

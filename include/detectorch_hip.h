@@ -122,7 +122,11 @@ int dtc_nms(const float* dets, int n, float thresh, void* workspace, size_t work
  * lib/utils/result_utils.py:126-143.  boxes float32 [n_seg, n_stride, 4] sorted by score descending inside each
  * segment; counts int32 [n_seg] (NULL: all n_stride valid; a NEGATIVE count marks a segment that is already reduced: its
  * keep / keep_count are left untouched).  keep int32 [n_seg, keep_stride] receives the kept
- * POSITIONS in score order, at most max_keep (>0) of them (== keep[:post_nms_top_n]); keep_count int32 [n_seg]. */
+ * POSITIONS in score order, at most max_keep (>0) of them (== keep[:post_nms_top_n]); keep_count int32 [n_seg].
+ * keep_stride caps the kept positions when max_keep is 0 or larger than it: at most
+ * cap = max_keep > 0 ? min(max_keep, keep_stride) : keep_stride positions are written per segment, the first cap of the greedy
+ * walk, and keep_count <= cap; entries of keep past keep_count are left untouched.  The workspace needs no initialisation: no
+ * word of it is read before this call has written it, whatever the counts. */
 size_t dtc_nms_sorted_workspace_bytes(int n_seg, int n_stride);
 int dtc_nms_sorted(const float* boxes, const int32_t* counts, int n_seg, int n_stride, float thresh, int max_keep,
                    void* workspace, size_t workspace_bytes, int32_t* keep, int keep_stride, int32_t* keep_count,
@@ -528,7 +532,10 @@ int dtc_prep_images(const dtc_image* images, int batch, const double* pixel_mean
 
 /* Drop-in for cython_nms.soft_nms(boxes_in, sigma, Nt, threshold, method)  lib/utils_cython/cython_nms.pyx:98-203 (entry
  * lib/utils/boxes.py:339-356; method 0 hard / 1 linear / 2 gaussian).  dets float32 [n,5] on the device (not modified);
- * dets_out [n,5] and inds_out int64 [n] receive the N' surviving rows in SELECTION order, n_out int32 [1] = N'. n <= 6000. */
+ * dets_out [n,5] and inds_out int64 [n] receive the N' surviving rows in SELECTION order, n_out int32 [1] = N'. n <= 6000.
+ * Equal scores: the first maximum in row order is picked (:128-132).  NaN scores behave as in the reference's
+ * `maxscore < boxes[pos, 4]` scan: the i-th pick is row i itself when its score is NaN, otherwise the first maximum of the
+ * non-NaN scores; a NaN score is never below score_thresh, so such rows survive, with the NaN in dets_out. */
 int dtc_soft_nms(const float* dets, int n, float sigma, float overlap_thresh, float score_thresh, int method,
                  float* dets_out, int64_t* inds_out, int32_t* n_out, dtc_stream_t stream);
 

@@ -163,6 +163,28 @@ def test_empty_and_single_candidate_segments(hip, oracle):
         assert int(out[2][1]) == 0 and int(out[2][2]) == 0
 
 
+@pytest.mark.parametrize("method", ["linear", "gaussian", "hard"])
+def test_soft_nms_tied_scores_within_a_class(hip, oracle, method):
+    """class scores quantised to 1/64 above the score threshold: every class has candidates with exactly equal scores, so the
+    first-maximum rule of the shared walk (soft_nms_walk.h, cython_nms.pyx:128-132) decides picks in det_soft_nms_kernel too"""
+    rs = synth.rng(35, 0)
+    B, R, ncls = 2, 400, 4
+    scores = (rs.uniform(0, 1, (B, R, ncls)) ** 3).astype(np.float32)
+    scores = np.where(scores > np.float32(0.05), np.ceil(scores * 64) / 64, scores).astype(np.float32)
+    boxes = np.stack([np.hstack([synth.make_rois(rs, R, min_side=60, max_side=400) for _ in range(ncls)]) for _ in range(B)])
+    boxes = boxes.astype(np.float32)
+    for b in range(B):
+        for j in range(1, ncls):
+            cand = scores[b, :, j][scores[b, :, j] > np.float32(0.05)]
+            assert cand.size > 100 and np.unique(cand).size <= 64          # at most 64 distinct values: ties in every class
+    out = hip.box_results_nms_limit(cu(scores), cu(boxes), max_det=100, max_out=512, **kwargs_of(method, None))
+    torch.cuda.synchronize()
+    for b in range(B):
+        ref, ref_roi = compose(oracle, scores[b], boxes[b], method, None)
+        assert ref.shape[0] >= 100
+        check_image((out[0], out[1], None, out[2]), b, ref, ref_roi, 512)
+
+
 @pytest.mark.parametrize("ncls", [2, 257])
 def test_class_count_limits(hip, oracle, ncls):
     rs = synth.rng(34, ncls)

@@ -50,6 +50,82 @@ def test_nms_threshold_boundary_set_vs_reference_cython(oracle, ref):
         assert np.array_equal(oracle.nms(d, thr), cn.nms(d, np.float32(thr))), thr
 
 
+@pytest.mark.parametrize("kind", ["default", "sparse"])
+@pytest.mark.parametrize("n", [8193, 12000, 16384])
+def test_nms_vs_reference_cython_above_8192_rows(oracle, ref, n, kind):
+    """the inputs of tests/test_hip_nms_limits.py, part a: oracle == the reference's Cython up to the 16384 rows dtc_nms accepts"""
+    import nms_limit_cases as lc
+    cn, _ = ref.load_ref_cython()
+    d = lc.big_dets(n, kind)
+    for thr in (0.5, 0.7):
+        assert np.array_equal(oracle.nms(d, thr), cn.nms(d, np.float32(thr))), thr
+
+
+def test_nms_limit_cases_are_really_there(oracle):
+    """more than 8192 survivors (words 128.. of the walk's bit vector hold KEPT rows, the finalize sort takes 16 keys per thread), fewer
+    than 8192 (it takes 8), nearly all rows (the reduce ORs rows of every block)"""
+    import nms_limit_cases as lc
+    d = lc.big_dets(16384, "default")
+    assert len(oracle.nms(d, 0.7)) > 8192
+    assert len(oracle.nms(d, 0.5)) < 8192
+    assert len(oracle.nms(lc.big_dets(16384, "sparse"), 0.5)) > 15000
+    for n in lc.TIED_SIZES:
+        assert np.unique(lc.big_dets(n, "tied")[:, 4]).size <= 33 and np.unique(lc.big_dets(n, "all_equal")[:, 4]).size == 1
+
+
+def test_nms_nonfinite_boxes_vs_reference_cython(oracle, ref):
+    """+-inf, nan and overflowing coordinates: oracle == the reference's Cython at every threshold the GPU test runs"""
+    from conftest import BOUNDARY_THRESHOLDS
+    import nms_limit_cases as lc
+    cn, _ = ref.load_ref_cython()
+    d = lc.nonfinite_box_dets()
+    assert np.isnan(d[:, :4]).any() and np.isinf(d[:, :4]).any() and np.unique(d[:, 4]).size == d.shape[0]
+    with np.errstate(all="ignore"):
+        for thr in (0.3, 0.5, 0.7) + tuple(t for t in BOUNDARY_THRESHOLDS if t <= 0):
+            assert np.array_equal(oracle.nms(d, thr), cn.nms(d, np.float32(thr))), thr
+
+
+def test_nms_odd_scores_vs_reference_cython(oracle, ref):
+    """+-inf, -0.0, negative and denormal scores.  Tie-free: oracle == the reference's Cython.  With runs of equal scores (-0.0 == +0.0
+    among them) the canonical rule (score descending, index ascending) differs from the reference's on purpose: oracle == a greedy NMS
+    in that order, as in test_hip_nms.test_tie_break_orders."""
+    import nms_limit_cases as lc
+    from test_hip_nms import _greedy_nms
+    cn, _ = ref.load_ref_cython()
+    d = lc.odd_score_dets(tie_free=True)
+    assert np.unique(d[:, 4]).size == d.shape[0] and not np.isnan(d[:, 4]).any()
+    for thr in (0.3, 0.5, 0.7):
+        assert np.array_equal(oracle.nms(d, thr), cn.nms(d, np.float32(thr))), thr
+    d = lc.odd_score_dets()
+    s = d[:, 4]
+    assert np.isposinf(s).sum() == 2 and np.isneginf(s).sum() == 2 and (s < 0).any() and (s == np.float32(1e-42)).any()
+    assert (np.signbit(s) & (s == 0)).any() and (~np.signbit(s) & (s == 0)).any() and not np.isnan(s).any()
+    order = np.lexsort((np.arange(d.shape[0]), -s))
+    for thr in (0.3, 0.5, 0.7):
+        assert np.array_equal(oracle.nms(d, thr), _greedy_nms(d, thr, list(order))), thr
+
+
+@pytest.mark.parametrize("method", ["hard", "linear", "gaussian"])
+def test_soft_nms_limit_cases_vs_reference_cython(oracle, ref, method):
+    """the inputs of tests/test_hip_nms_limits.py, part g (tied, non-finite and NaN scores, non-finite boxes, score thresholds):
+    oracle == the reference's Cython, NaN compared as NaN.  The 6000-row cases are left out: the Cython needs 13-20 s per method."""
+    import nms_limit_cases as lc
+    cn, _ = ref.load_ref_cython()
+    m = {"hard": 0, "linear": 1, "gaussian": 2}[method]
+    ran = 0
+    for name, (dets, kw) in lc.soft_cases().items():
+        if dets.shape[0] > 1500:
+            continue
+        with np.errstate(all="ignore"):
+            rd, rk = cn.soft_nms(dets.copy(), np.float32(kw["sigma"]), np.float32(kw["overlap_thresh"]), np.float32(kw["score_thresh"]),
+                                 np.uint8(m))
+        d, k = oracle.soft_nms(dets, kw["sigma"], kw["overlap_thresh"], kw["score_thresh"], method)
+        assert np.array_equal(k, np.asarray(rk, np.int64)), name
+        assert lc.same_rows(d, rd), name
+        ran += 1
+    assert ran >= 9
+
+
 @pytest.mark.parametrize("method", ["hard", "linear", "gaussian"])
 def test_soft_nms_vs_reference_cython(oracle, ref, method):
     cn, _ = ref.load_ref_cython()
