@@ -35,7 +35,6 @@
 #include "wave_ops.h"
 
 namespace dtc {
-DTC_PT_TABLE(detections)
 
 constexpr int kDetThreads = 256;
 constexpr int kNmsLdsCap = 512;       // candidates of a (class, image) segment whose boxes the in-workgroup NMS keeps in LDS
@@ -105,8 +104,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
   const int nr = p.n_rois ? min(p.n_rois[b], p.R) : p.R;
   const float* sc = p.cls_score + (size_t)b * p.R * p.n_cls + j;
   float* qs = p.q_scores + (size_t)seg * p.R;
-  [[maybe_unused]] const int ptb = blockIdx.y * gridDim.x + blockIdx.x;
-  DTC_PT(0, ptb, 0);
   if (tid == 0) running = 0;
   __syncthreads();
   // compaction of {r : scores[r, j] > thresh}  (np.where, result_utils.py:127).  Round 6: UNORDERED -- a wave claims its slots with
@@ -154,7 +151,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     p.cand_count[seg] = n;
     if (n == 0) p.keep_count[seg] = 0;
   }
-  DTC_PT(0, ptb, 1);
   const int nw = (nr + 63) >> 6;
   if (p.cand_bits)
     for (int w = tid; w < nw; w += kDetThreads) p.cand_bits[(size_t)seg * kCandWords + w] = cbits_s[w];
@@ -191,7 +187,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
   const int np2 = next_pow2(n);
   for (int i = n + tid; i < np2; i += kDetThreads) keys[i] = kPadKey;
   block_bitonic_sort<kDetThreads>(keys, np2);
-  DTC_PT(0, ptb, 2);
   // the box of rank k (decoded once): to q_boxes[r] for det_finalize, and in SCORE order for the NMS below -- in LDS when the segment
   // has at most kNmsLdsCap candidates (the usual tens to a few hundred), else in the global scratch p.sorted_boxes (LDS sized for
   // every possible segment would leave 2 workgroups per CU)
@@ -205,7 +200,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     if (in_lds) sbox_l[k] = v; else sorted_g[k] = v;         // score order (the NMS)
   }
   __syncthreads();
-  DTC_PT(0, ptb, 3);
   // ---- the segment's hard NMS, here (cython_nms.pyx:37-87: greedy over the score order; the kept box of rank i suppresses every
   // later box j with inter / (area_i + area_j - inter) >= thresh, IEEE division).  The class segments of a detection batch hold tens
   // of candidates (one 64-row block); as a separate launch pair (mask tiles + reduce over 640 segments) they cost 25 us of which
@@ -221,7 +215,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     __shared__ uint64_t keptm_s;
     __shared__ int kept_s;
     const int ncb = (n + 63) >> 6;
-    DTC_PT(0, ptb, 5);
     for (int wd = tid; wd < ncb; wd += kDetThreads) removed[wd] = 0ull;
     if (tid == 0) kept_s = 0;
     __syncthreads();
@@ -256,7 +249,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       }
       diag_s[wv][lane] = part;
       __syncthreads();
-      DTC_PT(0, ptb, 6 + 3 * min(rb, 2));
       // (2) greedy walk of the block (wave 0): a row is kept iff no earlier kept row (earlier blocks: `removed`) suppresses it
       if (wv == 0) {
         const uint64_t colword = (uint64_t)diag_s[0][lane] | ((uint64_t)diag_s[1][lane] << 16) | ((uint64_t)diag_s[2][lane] << 32) |
@@ -277,7 +269,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
         if (lane == 0) { keptm_s = keptm; kept_s = base + __builtin_popcountll(keptm); }
       }
       __syncthreads();
-      DTC_PT(0, ptb, 7 + 3 * min(rb, 2));
       // (3) the kept rows of this block against every later column: a wave takes one 64-column word per step
       const uint64_t keptm = keptm_s;
       // wave wv takes the block's rows [16 wv, 16 wv + 16) against EVERY later 64-column word (lane <-> column): a segment of ~100
@@ -302,7 +293,6 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
     };
     if (in_lds) run_blocks(std::true_type{}); else run_blocks(std::false_type{});
     if (tid == 0) p.keep_count[seg] = kept_s;
-    DTC_PT(0, ptb, 15);
   }
 }
 
@@ -462,7 +452,6 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
   constexpr int NWV = kFinThreads / 64, kClsPerWave = kFinMaxCls / NWV;
   const int nseg = p.n_cls - 1;
   const int seg0 = b * nseg;
-  DTC_PT(1, b, 0);
   // Round 6: ONE global round trip in front of the LDS phases instead of three dependent ones (counts -> prefix -> binary search ->
   // keys: 6 us of this kernel's 20).  Wave w owns classes w, w + 16, ...: it requests the class's kept count AND, speculatively, the
   // first 64 kept keys of the class (the array is [S, R]: the addresses are valid whatever the count is; a class keeps a few dozen
@@ -515,7 +504,6 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
     }
     __syncthreads();
   }
-  DTC_PT(1, b, 1);
   // ---- per-image limit (result_utils.py:154-163): threshold = max_det-th largest kept score ----
   uint32_t T = 0;  // ordered-key threshold; 0 == keep everything
   if (p.max_det > 0 && total > p.max_det) {
@@ -540,7 +528,6 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
     T = prefix;
   }
   __syncthreads();
-  DTC_PT(1, b, 2);
   const float sf = p.scale ? p.scale[b] : 1.f;
   float4* sbox_fm = reinterpret_cast<float4*>(&bitmap[0][0]);     // fast path + fm.on: the scaled boxes by output row (max_out <= 512)
   // one detection row (:143 dets_j[keep], :165 vstack).  Soft segments: `e` is the position in the class's kept list (selection
@@ -604,7 +591,6 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
       __syncthreads();
       fpn_map_rows(p.fm, b, p.max_out, min(nsurv, p.max_out), [&](int t) { return sbox_fm[t]; }, h0, h1);
     }
-    DTC_PT(1, b, 5);
     return;
   }
   // ---- general path: more survivors than the list holds (max_det <= 0 on a large head, mass ties) or entries not staged ----
@@ -625,13 +611,11 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
     if (lane == 0) ccnt[c] = cnt;
   }
   __syncthreads();
-  DTC_PT(1, b, 3);
   if (wv == 0) {
     fin_prefix(coff, [&](int c) { return c < nseg ? ccnt[c] : 0; }, nseg, lane);
     if (lane == 0) p.det_count[b] = coff[nseg];
   }
   __syncthreads();
-  DTC_PT(1, b, 4);
   // ---- pass B: class-major, candidate(roi)-ascending output (:143 dets_j[keep], :165 vstack) ----
   for (int c = wv; c < nseg; c += kFinThreads / 64) {
     const int nk = koff[c + 1] - koff[c];
@@ -691,7 +675,6 @@ __global__ __launch_bounds__(kFinThreads) void det_finalize_kernel(FinParams p, 
     fpn_map_rows(p.fm, b, p.max_out, min(coff[nseg], p.max_out),
                  [&](int t) { return make_float4(ld(ds + 4 * t), ld(ds + 4 * t + 1), ld(ds + 4 * t + 2), ld(ds + 4 * t + 3)); }, h0, h1);
   }
-  DTC_PT(1, b, 5);
 }
 
 // ---- bbox voting of the emitted rows (box_utils.box_voting(nms_dets, dets_j, thresh, 'ID'), result_utils.py:145-151): one wavefront per

@@ -16,7 +16,6 @@
 #include "wave_ops.h"
 
 namespace dtc {
-DTC_PT_TABLE(fpn)
 
 constexpr int kFpnThreads = 1024;
 constexpr int kFpnMaxLevels = 8;
@@ -275,7 +274,6 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
   __shared__ int wave_cnt[kFpnMaxLevels][R * kFpnThreads / 64];              // per (level, rank-wave): rank-wave = rr * 16 + wave
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int nl_out = p.k_max - p.k_min + 1;
-  DTC_PT(p.L_in > 1 ? 0 : 1, b, 0);
   if (tid < p.L_in) cnt_s[tid] = min(p.in_counts[b * p.L_in + tid], p.P);
   // Round 6: the scores of EVERY row of every input list (n_max = L_in * P <= 8192: up to eight per thread) are requested before the
   // lists' counts are known -- one global round trip in front of the merge instead of two dependent ones; rows past a count hold
@@ -374,7 +372,6 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
     for (int r = tid; r < m; r += kFpnThreads) src_of_rank[r] = (int)desc_key_index(kbuf[l_off[0] + r]);
     __syncthreads();
   }
-  DTC_PT(p.L_in > 1 ? 0 : 1, b, 1);
   // ---- rank r: roi, level, position inside its level -- all in registers from here on ---------------------------------
   constexpr int kRW = kFpnThreads / 64;                                        // waves per round of ranks
   int lvl[R], my_before[R];
@@ -457,7 +454,6 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
   if (tid == 0) p.n_out[b] = m;
   if (!p.roi_order) return;
   __syncthreads();
-  DTC_PT(p.L_in > 1 ? 0 : 1, b, 2);
   // Rank of this RoI's key among all keys (they are unique).  Round 2 counted `key' < key` over ALL top_n keys per thread
   // (250 broadcast ds_read_b128 + 1000 compares each: the longest phase of the kernel); the key's top 9 bits (level | band)
   // name one of a few dozen populated buckets of ~75 RoIs, so: histogram -> exclusive scan -> members placed bucket by
@@ -501,7 +497,6 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_collect_fast_kernel(FpnParams
       }
     }
   }
-  DTC_PT(p.L_in > 1 ? 0 : 1, b, 3);
 }
 
 }  // namespace dtc

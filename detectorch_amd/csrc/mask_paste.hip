@@ -17,8 +17,6 @@
 
 namespace dtc {
 
-DTC_PT_TABLE(mask_paste)
-
 constexpr int kPasteThreads = 256;
 constexpr int kMaxMaskSide = 64;   // M + 2 <= 64
 constexpr int kBandPixels = 4096;  // a detection's paste rectangle is cut into row bands of about this many pixels ...
@@ -116,9 +114,6 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_kernel(PasteParams p
   const int wg = is_helper ? p.max_out + (int)blockIdx.x : (int)blockIdx.x - (helpers ? kHelpers : 0);   // main: detection index
   if (is_helper ? (!helpers || nd == 0) : (wg >= nd && wg != 0)) return;
   const int im_h = (int)p.im_size[b * 2 + 0], im_w = (int)p.im_size[b * 2 + 1];
-  const int ptk = is_helper ? 1 : 0, ptb = b == 0 ? (int)blockIdx.x - (is_helper ? 0 : kHelpers) : 1 << 20;   // phase trace: image 0 only
-  (void)ptk; (void)ptb;
-  DTC_PT(ptk, ptb, 0);
 
   // ---- per-image tables (every live workgroup: same inputs, same results) ---------------------------------------------------
   long long my_off = 0, total = 0;
@@ -168,7 +163,6 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_kernel(PasteParams p
     my_off = (wg == 0) ? 0 : total;
   }
   if (wg == 0 && tid == 0) p.mask_bytes[b] = total;
-  DTC_PT(ptk, ptb, 1);
   if (!is_helper && wg >= nd) return;
 
   // ---- items of this workgroup: (detection, band) ---------------------------------------------------------------------------
@@ -224,7 +218,6 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_kernel(PasteParams p
       }
     }
     __syncthreads();
-    DTC_PT(ptk, ptb, 2);
     // From here on the wavefronts work on their own: a share is a 64-column chunk of the rectangle x a part of the band's rows
     // (narrow rectangles split the rows over the waves instead of leaving waves idle); a lane only reads the hcol column it wrote.
     const int ncc = (rw + 63) >> 6;
@@ -274,7 +267,6 @@ __global__ __launch_bounds__(kPasteThreads) void mask_paste_kernel(PasteParams p
     }
   }
   __syncthreads();
-  DTC_PT(ptk, ptb, 3);
 }
 
 }  // namespace dtc

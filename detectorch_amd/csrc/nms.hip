@@ -26,7 +26,6 @@
 
 namespace dtc {
 
-DTC_PT_TABLE(nms)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1. segment sort.  scores [S, n_stride] (+counts) -> order [S, n_stride] int32 (original index of the k-th best),
@@ -323,7 +322,6 @@ __global__ __launch_bounds__(kReduceLdsThreads) void nms_reduce_lds_kernel(const
   const int cap = max_keep > 0 ? min(max_keep, keep_stride) : keep_stride;
   uint64_t* Ml = reinterpret_cast<uint64_t*>(reduce_smem);
   uint64_t* DTl = Ml + (size_t)nrow_pad * ncb_stride;
-  DTC_PT(0, s, 0);
   if (tid < 256) removed[tid] = 0;
   int n;
   {
@@ -367,7 +365,6 @@ __global__ __launch_bounds__(kReduceLdsThreads) void nms_reduce_lds_kernel(const
   }
   const int ncb = (n + 63) >> 6;
   __syncthreads();
-  DTC_PT(0, s, 1);
   if (tid >= 64) return;                       // the serial part belongs to wavefront 0: no workgroup barrier below
   int kept = 0;
   // byte address of this lane's word of row rg in LDS; row block rb, row 4k + rg, column chunk cbase: + the offsets below
@@ -435,7 +432,6 @@ __global__ __launch_bounds__(kReduceLdsThreads) void nms_reduce_lds_kernel(const
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
   if (lane == 0) keep_count[s] = kept;
-  DTC_PT(0, s, 2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

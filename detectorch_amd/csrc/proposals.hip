@@ -26,7 +26,6 @@
 #include <stdlib.h>
 
 namespace dtc {
-DTC_PT_TABLE(proposals)
 
 constexpr int kRpnMaxLevels = 8;
 constexpr int kRpnMaxAnchors = 16;
@@ -170,8 +169,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_hist_kernel(RpnParams p) {
   if (ext.K >= ext.N) return;  // take everything: no selection needed
   const int seg = b * p.n_levels + l;
   const int chunk = blockIdx.x - L.chunk_begin;
-  [[maybe_unused]] const int ptb = blockIdx.y * gridDim.x + blockIdx.x;
-  DTC_PT(PASS, ptb, 0);
   // the chunk's 16 scores per thread are requested FIRST (independent loads, back to back) and consumed after the histogram
   // is cleared and the previous pass' digit is known: the load latency hides behind that work.  (A load -> LDS atomic loop
   // paid one L2 round trip per element: 7.4 of the kernel's 9.2 us.)
@@ -186,7 +183,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_hist_kernel(RpnParams p) {
   for (int i = threadIdx.x; i < kHistBins; i += kHistThreads) h[i] = 0;
   const SelState st = load_state<PASS>(p, seg, (uint32_t)ext.K, sh);  // ends with a barrier (or needs one for PASS 0)
   if (PASS == 0) __syncthreads();
-  DTC_PT(PASS, ptb, 1);
 #pragma unroll
   for (int u = 0; u < kChunk / kHistThreads; u++) {
     const int i = begin + u * kHistThreads + (int)threadIdx.x;
@@ -197,13 +193,11 @@ __global__ __launch_bounds__(kHistThreads) void rpn_hist_kernel(RpnParams p) {
     }
   }
   __syncthreads();
-  DTC_PT(PASS, ptb, 2);
   uint32_t* G = p.hist + ((size_t)seg * 2 + PASS) * kHistBins;
   for (int i = threadIdx.x; i < kHistBins; i += kHistThreads) {
     const uint32_t v = h[i];
     if (v) atomicAdd(&G[i], v);
   }
-  DTC_PT(PASS, ptb, 3);
 }
 
 __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) {
@@ -221,8 +215,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
   const int chunk = blockIdx.x - L.chunk_begin;
   const SegExtent ext = seg_extent(p, b, L);
   const bool take_all = ext.K >= ext.N;
-  [[maybe_unused]] const int ptb = blockIdx.y * gridDim.x + blockIdx.x;
-  DTC_PT(2, ptb, 0);
   const float* sc = L.cls + (size_t)b * L.N;      // the chunk's scores: requested first, consumed behind the threshold look-up
   const int begin = chunk * kChunk, end = min(begin + kChunk, L.N);
   float v[kChunk / kHistThreads];
@@ -239,7 +231,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
     kb = candidate_band(bl, bl | 0xffu, L.logit != 0, sh);
   }
   __syncthreads();
-  DTC_PT(2, ptb, 1);
   const int HW = L.H * L.W;
 #pragma unroll
   for (int u = 0; u < kChunk / kHistThreads; u++) {
@@ -259,7 +250,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
     }
   }
   __syncthreads();
-  DTC_PT(2, ptb, 2);
   uint32_t* cnt = p.counters + (size_t)seg * 2;
   if (threadIdx.x < 2) gbase[threadIdx.x] = lcnt[threadIdx.x] ? atomicAdd(&cnt[threadIdx.x], lcnt[threadIdx.x]) : 0u;
   __syncthreads();
@@ -268,7 +258,6 @@ __global__ __launch_bounds__(kHistThreads) void rpn_compact_kernel(RpnParams p) 
   for (uint32_t j = threadIdx.x; j < lcnt[0]; j += kHistThreads)
     if (gbase[0] + j < (uint32_t)p.k_stride) gt[gbase[0] + j] = stage[j];
   for (uint32_t j = threadIdx.x; j < lcnt[1]; j += kHistThreads) cand[gbase[1] + j] = stage[kChunk - 1 - j];
-  DTC_PT(2, ptb, 3);
 }
 
 // generate_proposals.py:165-214 (weights (1,1,1,1)) + :216-238 + :151-163
@@ -325,7 +314,6 @@ __global__ __launch_bounds__(kSortDecodeThreads) void rpn_sort_kernel(RpnParams 
   const int b = seg / p.n_levels, l = seg - b * p.n_levels;
   const RpnLevelDev& L = p.lv[l];
   const int tid = threadIdx.x;
-  DTC_PT(3, seg, 0);
   const uint32_t n_gt = min(p.counters[(size_t)seg * 2], (uint32_t)p.k_stride);
   const uint32_t n_cand = p.counters[(size_t)seg * 2 + 1];
   const uint64_t* gt = p.gt_keys + (size_t)seg * p.k_stride;
@@ -380,7 +368,6 @@ __global__ __launch_bounds__(kSortDecodeThreads) void rpn_sort_kernel(RpnParams 
     }
   }
   __syncthreads();
-  DTC_PT(3, seg, 1);
   const uint64_t* sorted = keys;
   if (np2 > 2048 && rpn_sort_radix_capable(sort_cap)) {
     // long segments (C4: 6000 ranks; up to 8192 keys -- beyond that the two key buffers do not fit LDS: bitonic): LSD radix sort over the score word and the index bits in use, 6 passes instead of the 91
@@ -394,14 +381,12 @@ __global__ __launch_bounds__(kSortDecodeThreads) void rpn_sort_kernel(RpnParams 
   } else {
     block_bitonic_sort<kSortDecodeThreads>(keys, np2);
   }
-  DTC_PT(3, seg, 2);
 
   // the first K keys are the answer: hand them to rpn_decode (a segment's 6000 ranks are decoded by 24 workgroups, not by this one)
   const int n_rank = min(K, total);
   uint64_t* sk = p.sorted_keys + (size_t)seg * p.k_stride;
   for (int k = tid; k < n_rank; k += kSortDecodeThreads) sk[k] = sorted[k];
   if (tid == 0) p.n_rank[seg] = n_rank;
-  DTC_PT(3, seg, 3);
 }
 
 // ranks [0, K) in score order: decode, clip, filter, ORDERED compaction -- spread over the chip.  Round 4 measured the decode of a

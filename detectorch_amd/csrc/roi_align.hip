@@ -24,8 +24,10 @@
 // The default for the FPN heads (NCHW features, sampling_ratio 2) is the cluster-stationary kernel in roi_align_tile.hip,
 // for single-level inputs with adaptive sampling (the C4 heads) the map-stationary kernel in roi_align_map.hip.
 // Knobs (resolved once per process): RoiAlignKnobs in roi_align_common.h, read by roi_align_knobs() below.  DESIGN.md
-// section 3.1 keeps the numbers of the variants that measured slower (wave-specialised loader/compute waves, LDS-DMA staging,
-// 16-byte row pieces, row-slot chunking, quad-aligned windows, pixel-pair loads).
+// section 3.1 keeps the numbers of the variants that were built, measured slower and removed (wave-specialised loader/compute
+// waves, LDS-DMA staging, 16-byte row pieces, row-slot chunking, quad-aligned windows, pixel-pair loads).  The scripts that set
+// the knobs of the row-piece, row-slot and quad variants (tools/tcp_probe*.sh) and a compile-time override of this kernel's waves
+// per SIMD went later, with the other diagnostic builds: the last commit that has them is 7c22f5a.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -370,11 +372,9 @@ __device__ __forceinline__ void run_passes(Stager& st, LdsGeom& G, const dtc_fea
  }
 }
 
-#ifndef DTC_RA_WAVES
-#define DTC_RA_WAVES 2
-#endif
+constexpr int kLdsKernelWaves = 2;      // waves per SIMD roi_align_fwd_lds is compiled for (register budget)
 template <typename TIn, typename TOut>
-__global__ __launch_bounds__(kRoiAlignThreads, DTC_RA_WAVES) void roi_align_fwd_lds(RoiAlignParams p, int lds_floats) {
+__global__ __launch_bounds__(kRoiAlignThreads, kLdsKernelWaves) void roi_align_fwd_lds(RoiAlignParams p, int lds_floats) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* lds = reinterpret_cast<float*>(smem);
   AxisEntry* ytab = reinterpret_cast<AxisEntry*>(smem);
@@ -716,8 +716,6 @@ const RoiAlignKnobs& roi_align_knobs() {
     k.nhwc_lds = number("DTC_RA_NHWC_LDS", 1) != 0;
     k.nhwc_lds_kb = in_range("DTC_RA_NHWC_LDS_KB", 24, 160, 0);
     k.nhwc_pipe = in_range("DTC_RA_NHWC_PIPE", 0, 2, 1);
-    k.nhwc_pipe16 = number("DTC_RA_NHWC_PIPE16", 0) != 0;
-    k.nhwc_lds_16bit = number("DTC_RA_NHWC_LDS_16BIT", 0) != 0;
     return k;
   }();
   return knobs;

@@ -138,7 +138,7 @@ template <> __device__ __forceinline__ f32x2 mul_pair16<float>(uint32_t, float) 
 template <typename T> __device__ __forceinline__ void fma_pair16(f32x2& acc, uint32_t u, float w);
 template <> __device__ __forceinline__ void fma_pair16<__half>(f32x2& acc, uint32_t u, float w) {
   asm("v_fma_mix_f32 %0, %2, %3, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %1, %2, %3, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "+v"(acc.x), "+v"(acc.y) : "v"(u), "v"(w));
+      : "+&v"(acc.x), "+&v"(acc.y) : "v"(u), "v"(w));
 }
 template <> __device__ __forceinline__ void fma_pair16<bf16_t>(f32x2& acc, uint32_t u, float w) {
   const f32x2 v = {__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
@@ -190,12 +190,10 @@ struct RoiAlignKnobs {
   // map-stationary kernel (roi_align_map.hip)
   bool map_prep = true;        // DTC_RA_MAP_PREP=n, off when atoi == 0: the per-launch preparation pass
   bool map_pitch = true;       // DTC_RA_MAP_PITCH=0: LDS image rows W slots apart instead of W + 1
-  // channels_last LDS-DMA kernels (roi_align_nhwc.hip)
+  // channels_last LDS-DMA kernels (roi_align_nhwc.hip; float32 maps only)
   int nhwc_lds = 1;            // DTC_RA_NHWC_LDS=n, atoi != 0: 0 takes neither kernel
   int nhwc_lds_kb = 0;         // DTC_RA_NHWC_LDS_KB=n, 24..160: LDS per workgroup (0: 40, pipelined kernel 78)
   int nhwc_pipe = 1;           // DTC_RA_NHWC_PIPE=n, 0..2: pipelined kernel never / by bin count (> 64) / always
-  int nhwc_pipe16 = 0;         // DTC_RA_NHWC_PIPE16=n, atoi != 0: the pipelined kernel for 16-bit maps too
-  bool nhwc_lds_16bit = false; // DTC_RA_NHWC_LDS_16BIT=n, atoi != 0: the LDS-DMA kernel for 16-bit maps too
 };
 const RoiAlignKnobs& roi_align_knobs();
 
@@ -210,7 +208,7 @@ int roi_align_get_exact();
 size_t roi_align_map_workspace_bytes(int n_rois);      // per-launch preparation records (optional: workspace == nullptr -> none)
 int launch_roi_align_map_ws(const RoiAlignParams& p, int in_dtype, int out_dtype, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
-// launchers of the channels_last kernel with an LDS-DMA staged window (roi_align_nhwc.hip): sampling_ratio 2, <= 64 bins
+// launchers of the float32 channels_last kernels with an LDS-DMA staged window (roi_align_nhwc.hip): sampling_ratio 2
 bool roi_align_nhwc_lds_supported(const RoiAlignParams& p, int in_dtype, int out_dtype);
 int launch_roi_align_nhwc_lds(const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t stream);
 

@@ -1,5 +1,6 @@
-// A1  RoIAlign forward for gfx950 -- channels_last (NHWC) feature maps, sampling_ratio 2, <= 64 bins (the FPN box head when the
-// backbone emits channels_last tensors: MIOpen's preferred layout for 16-bit convolutions on MI355X).
+// A1  RoIAlign forward for gfx950 -- float32 channels_last (NHWC) feature maps, sampling_ratio 2 (the FPN heads when the backbone
+// emits channels_last tensors).  16-bit channels_last maps never come here: the direct-gather kernels serve them (16-bit instances
+// of both kernels of this file measured 0.35 ms against 0.27 ms per box-head launch, tools/r04/README.md, and were removed).
 //
 // Replaces roi_align_forward_kernel (lib/cppcuda/roi_align_forward_cuda.cu:82-159); bit-compatible with the CPU path
 // roi_align_forward_loop (lib/cppcuda_cffi/src/cpp/roi_align_cpu_loop.cpp:118-219): same float32 operations, same order.
@@ -8,7 +9,7 @@
 // the transposing LDS commit (316 staged pixels per (RoI, channel), four ds_write_b32 per 16-byte piece) and the bank-conflicted
 // tap gather (lane <-> (RoI, bin): 9.5 LDS cycles per ds_read_b128 where 4 are conflict-free, tools/r03/lds_taps.py).  With the
 // channels innermost both disappear:
-//   * a pixel's 256-byte chunk (64 float32 / 128 16-bit channels) is contiguous in memory AND is what the LDS image wants
+//   * a pixel's 256-byte chunk (64 float32 channels) is contiguous in memory AND is what the LDS image wants
 //     ([pixel][channels]): the window is staged with LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane land lane-linear, four
 //     pixels per wave-instruction) -- no staging registers, no commit instructions, every fetched byte is used: 5.3 line fills
 //     per (RoI, channel) where the cluster kernel needs 9.9;
@@ -36,33 +37,13 @@ typedef __attribute__((address_space(1))) const void nl_glb_void;
 
 __device__ __forceinline__ int nl_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// 16 bytes of the LDS image -> the lane's channels as float32 (4 for float32 maps, 8 for 16-bit maps)
-template <typename TIn> struct NlLane;
-template <> struct NlLane<float> {
-  static constexpr int kCh = 4;
-  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[4]) {
-    v[0] = __uint_as_float(r.x); v[1] = __uint_as_float(r.y); v[2] = __uint_as_float(r.z); v[3] = __uint_as_float(r.w);
-  }
-};
-template <> struct NlLane<__half> {
-  static constexpr int kCh = 8;
-  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const __half2 h = *reinterpret_cast<const __half2*>(&w[i]);
-      v[2 * i] = __low2float(h); v[2 * i + 1] = __high2float(h);
-    }
-  }
-};
-template <> struct NlLane<bf16_t> {
-  static constexpr int kCh = 8;
-  static __device__ __forceinline__ void widen(const u32x4& r, float (&v)[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-  }
-};
+// float32 maps only: a lane's 16 bytes of a pixel are 4 channels, a workgroup's 256-byte chunk is 64 (16-bit channels_last maps are
+// served by the direct-gather kernels, roi_align_nhwc16.hip and roi_align.hip)
+constexpr int kNlLaneCh = 4;
+constexpr int kNlCb = 16 * kNlLaneCh;
+__device__ __forceinline__ void nl_widen(const u32x4& r, float (&v)[kNlLaneCh]) {
+  v[0] = __uint_as_float(r.x); v[1] = __uint_as_float(r.y); v[2] = __uint_as_float(r.z); v[3] = __uint_as_float(r.w);
+}
 
 template <typename TOut> __device__ __forceinline__ void nl_store4(TOut* d, float4 v);
 template <> __device__ __forceinline__ void nl_store4<float>(float* d, float4 v) { store_stream16(d, v); }     // streaming stores: dtc_common.h
@@ -76,11 +57,11 @@ template <> __device__ __forceinline__ void nl_store4<bf16_t>(bf16_t* d, float4 
 }
 
 
-template <typename TIn, typename TOut>
+template <typename TOut>
 __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignParams p, int img_pixels) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int CL = NlLane<TIn>::kCh;                 // channels per lane
-  constexpr int CB = 16 * CL;                           // channels per workgroup: one 256-byte chunk per pixel
+  constexpr int CL = kNlLaneCh;                         // channels per lane
+  constexpr int CB = kNlCb;                             // channels per workgroup: one 256-byte chunk per pixel
   const int bins = p.pooled_h * p.pooled_w;
   // [axis samples: 2 x 32 AxisEntry][bin records: bins x 96 B][slab: CB x bins float32][image: img_pixels x 256 B]
   AxisEntry* ytab = reinterpret_cast<AxisEntry*>(smem);
@@ -108,10 +89,10 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
   __syncthreads();
   const int x0 = xtab[0].lo, x1 = xtab[2 * p.pooled_w - 1].hi;        // sample positions are non-decreasing: first .lo / last .hi
   const int w = x1 - x0 + 1;
-  const TIn* fbase = reinterpret_cast<const TIn*>(L.data) + (int64_t)hd.b * L.stride_n + c0;
+  const float* fbase = reinterpret_cast<const float*>(L.data) + (int64_t)hd.b * L.stride_n + c0;
   // plain channels_last strides and 16-byte alignment: what the LDS-DMA staging needs
-  const bool dma_ok = L.stride_c == 1 && ((L.stride_w * (int64_t)sizeof(TIn)) & 15) == 0 && ((L.stride_h * (int64_t)sizeof(TIn)) & 15) == 0 &&
-                      ((L.stride_n * (int64_t)sizeof(TIn)) & 15) == 0 && (reinterpret_cast<uintptr_t>(L.data) & 15) == 0;
+  const bool dma_ok = L.stride_c == 1 && ((L.stride_w * (int64_t)sizeof(float)) & 15) == 0 && ((L.stride_h * (int64_t)sizeof(float)) & 15) == 0 &&
+                      ((L.stride_n * (int64_t)sizeof(float)) & 15) == 0 && (reinterpret_cast<uintptr_t>(L.data) & 15) == 0;
   const int q = lane & 15;                               // this lane's 16-byte chunk of a pixel
   const int slot = (tid >> 4);                           // bin slot 0..15 of the workgroup
 
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
         const int pi = min(4 * k + (lane >> 4), np - 1);               // pixels past the window repeat its last one
         const int row = (int)(((float)pi + 0.5f) * rw);                  // exact: pi < 2^13
         const int col = pi - row * w;
-        const TIn* g = fbase + (int64_t)(ys + row) * L.stride_h + (int64_t)(x0 + col) * L.stride_w;
+        const float* g = fbase + (int64_t)(ys + row) * L.stride_h + (int64_t)(x0 + col) * L.stride_w;
         __builtin_amdgcn_global_load_lds((nl_glb_void*)(reinterpret_cast<const char*>(g) + q * 16),
                                          (nl_lds_void*)(img + (size_t)k * 1024), 16, 0, 0);
       }
@@ -194,11 +175,11 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
               r4 = *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>(img32 + off.w + q * 16);
             } else {
               const char* gb = reinterpret_cast<const char*>(fbase) + q * 16;
-              auto ga = [&](uint32_t t) { return gb + ((int64_t)(t >> 16) * L.stride_h + (int64_t)(t & 0xffff) * L.stride_w) * (int64_t)sizeof(TIn); };
+              auto ga = [&](uint32_t t) { return gb + ((int64_t)(t >> 16) * L.stride_h + (int64_t)(t & 0xffff) * L.stride_w) * (int64_t)sizeof(float); };
               if (dma_ok) {
                 r1 = *reinterpret_cast<const u32x4*>(ga(off.x)); r2 = *reinterpret_cast<const u32x4*>(ga(off.y));
                 r3 = *reinterpret_cast<const u32x4*>(ga(off.z)); r4 = *reinterpret_cast<const u32x4*>(ga(off.w));
-              } else {      // unaligned chunks: 4-byte (2-byte) loads
+              } else {      // unaligned chunks: 4-byte loads
                 const uint32_t* a1 = reinterpret_cast<const uint32_t*>(ga(off.x)); const uint32_t* a2 = reinterpret_cast<const uint32_t*>(ga(off.y));
                 const uint32_t* a3 = reinterpret_cast<const uint32_t*>(ga(off.z)); const uint32_t* a4 = reinterpret_cast<const uint32_t*>(ga(off.w));
                 r1 = u32x4{a1[0], a1[1], a1[2], a1[3]}; r2 = u32x4{a2[0], a2[1], a2[2], a2[3]};
@@ -206,7 +187,7 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
               }
             }
             float v1[CL], v2[CL], v3[CL], v4[CL];
-            NlLane<TIn>::widen(r1, v1); NlLane<TIn>::widen(r2, v2); NlLane<TIn>::widen(r3, v3); NlLane<TIn>::widen(r4, v4);
+            nl_widen(r1, v1); nl_widen(r2, v2); nl_widen(r3, v3); nl_widen(r4, v4);
             const float w1 = yh[iy] * xh[ix], w2 = yh[iy] * xl[ix], w3 = yl[iy] * xh[ix], w4 = yl[iy] * xl[ix];   // :95
 #pragma unroll
             for (int c = 0; c < CL; c++) acc[c] += w1 * v1[c] + w2 * v2[c] + w3 * v3[c] + w4 * v4[c];               // :208-211
@@ -292,26 +273,11 @@ __device__ __forceinline__ void np_glds16s(uint32_t voff, const void* sbase_, ui
 
 struct __attribute__((packed, aligned(4))) NpF4 { float x, y, z, w; };     // 16-byte store at 4-byte alignment (global_store_dwordx4)
 
-// Development aid (-DDTC_NP_TRACE, tools/r04/np_trace.py): cycle counter of the planner's lane 0 and of the first pooler wave's
-// lane 0 at their phase boundaries, summed per phase.
-#ifdef DTC_NP_TRACE
-constexpr int kNpTraceSlots = 16;
-__device__ unsigned long long g_np_trace[2 * kNpTraceSlots * 4096];
-struct NpTrace {
-  unsigned long long last, acc[kNpTraceSlots];
-  __device__ __forceinline__ void start() { for (int i = 0; i < kNpTraceSlots; i++) acc[i] = 0; last = __builtin_readcyclecounter(); }
-  __device__ __forceinline__ void mark(int i) { const unsigned long long n = __builtin_readcyclecounter(); acc[i] += n - last; last = n; }
-};
-#define NP_MARK(i) tt.mark(i)
-#else
-#define NP_MARK(i) ((void)0)
-#endif
-
-template <typename TIn, bool DESC>      // DESC: packed descriptors (p.roi_desc) -- the only vector-memory reads are then the DMA
+template <bool DESC>      // DESC: packed descriptors (p.roi_desc) -- the only vector-memory reads are then the DMA
 __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlignParams p, int img_pixels) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int CL = NlLane<TIn>::kCh;                 // channels per lane
-  constexpr int CB = 16 * CL;                           // channels per item: one 256-byte chunk per pixel
+  constexpr int CL = kNlLaneCh;                         // channels per lane
+  constexpr int CB = kNlCb;                             // channels per item: one 256-byte chunk per pixel
   const int PH = p.pooled_h, PW = p.pooled_w, bins = PH * PW;
   // [axis tables: 3 slots][unit descriptors x 3][item globals x 3][transposition scratch: 7 waves x CB x 5 dwords][image 0][image 1]
   NpTab* tab = reinterpret_cast<NpTab*>(smem);                                             // [slot][y|x][32]
@@ -338,10 +304,6 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     first_item = blockIdx.x; item_end = n_items; step = gridDim.x;
   }
   if (first_item >= item_end) return;
-#ifdef DTC_NP_TRACE
-  NpTrace tt; tt.start();
-  unsigned long long n_units = 0, n_items_done = 0, n_dma = 0;
-#endif
 
   if (wv == 0) {
     // =================================================== the planner =========================================================
@@ -358,7 +320,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     RoiRaw raw_pre = load_raw(first_item / nct);      // descriptor of the next item to set up, fetched one item ahead
     // the item being planned (all uniform)
     int i_mode = 2, i_par = 0, i_x0 = 0, i_w = 1, i_y0 = 0;
-    const TIn* i_fbase = nullptr; int64_t i_sh = 0, i_sw = 0; float* i_out = nullptr;
+    const float* i_fbase = nullptr; int64_t i_sh = 0, i_sw = 0; float* i_out = nullptr;
     int ylo_r = 0, yhi_r = 0;       // its y samples in lanes 0 .. 2 PH - 1
     int next_par = 0;
     auto setup_item = [&](int wi) {
@@ -381,12 +343,12 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
       i_x0 = np_rl(e.lo, 32); i_y0 = np_rl(e.lo, 0);      // sample positions are non-decreasing: first .lo / last .hi
       const int x1 = np_rl(e.hi, nl_uni(32 + 2 * PW - 1));
       i_w = x1 - i_x0 + 1;
-      i_fbase = reinterpret_cast<const TIn*>(L.data) + (int64_t)nl_uni(hd.b) * L.stride_n + c0;
+      i_fbase = reinterpret_cast<const float*>(L.data) + (int64_t)nl_uni(hd.b) * L.stride_n + c0;
       i_sh = L.stride_h; i_sw = L.stride_w;
       // plain channels_last strides and 16-byte alignment: what the LDS-DMA staging needs
-      const bool dma_ok = L.stride_c == 1 && ((L.stride_w * (int64_t)sizeof(TIn)) & 15) == 0 && ((L.stride_h * (int64_t)sizeof(TIn)) & 15) == 0 &&
-                          ((L.stride_n * (int64_t)sizeof(TIn)) & 15) == 0 && (reinterpret_cast<uintptr_t>(L.data) & 15) == 0 &&
-                          L.stride_h > 0 && L.stride_w > 0 && (L.stride_h + L.stride_w) * (int64_t)sizeof(TIn) * (img_pixels + 4) < (1ll << 31);   // 32-bit lane offsets
+      const bool dma_ok = L.stride_c == 1 && ((L.stride_w * (int64_t)sizeof(float)) & 15) == 0 && ((L.stride_h * (int64_t)sizeof(float)) & 15) == 0 &&
+                          ((L.stride_n * (int64_t)sizeof(float)) & 15) == 0 && (reinterpret_cast<uintptr_t>(L.data) & 15) == 0 &&
+                          L.stride_h > 0 && L.stride_w > 0 && (L.stride_h + L.stride_w) * (int64_t)sizeof(float) * (img_pixels + 4) < (1ll << 31);   // 32-bit lane offsets
       i_mode = dma_ok ? 0 : 1;
       if (si < 2 * (isx ? PW : PH)) {
         const int o = (i_par * 2 + (isx ? 1 : 0)) * kNpTabEntries + si;
@@ -422,7 +384,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
         d.flags = 1 | (staged << 1) | ((pb >= PH ? 1 : 0) << 2) | (i_mode << 3) | (i_par << 5);
         d.rows = pa | (pb << 8);
         d.strip_off = (ys - i_y0) * i_w * kNlChunk; d.wh = i_w | (hs << 16);
-        d.shb = (int)(i_sh * (int64_t)sizeof(TIn)); d.swb = (int)(i_sw * (int64_t)sizeof(TIn));
+        d.shb = (int)(i_sh * (int64_t)sizeof(float)); d.swb = (int)(i_sw * (int64_t)sizeof(float));
         const uint64_t o = reinterpret_cast<uint64_t>(i_out);
         d.out_lo = (uint32_t)o; d.out_hi = (uint32_t)(o >> 32);
         const uint64_t wb = reinterpret_cast<uint64_t>(i_fbase + (int64_t)ys * i_sh + (int64_t)i_x0 * i_sw);
@@ -430,9 +392,6 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
         d.pad[0] = d.pad[1] = 0;
         ud[ds] = d;
       }
-#ifdef DTC_NP_TRACE
-      n_dma += (unsigned long long)(hs * i_w);
-#endif
       return pb;
     };
     // the unit after the one just planned: next strip, or first strip of the next item, or none
@@ -444,9 +403,6 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
       } else if (next_item < item_end) {
         setup_item(next_item); next_item += step;
         cur_pb = plan_unit(0, ds);
-#ifdef DTC_NP_TRACE
-        n_items_done++;
-#endif
       } else {
         if (lane == 0) ud[ds].flags = 0;
         more = 0;
@@ -458,24 +414,11 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     __syncthreads();                                        // P0
     int k = 0;
     while (true) {
-      NP_MARK(0);
       __syncthreads();                                        // T(k)
-      NP_MARK(2);
       if (!(nl_uni(ud[k % kNpSlots].flags) & 1)) break;
       plan_next((k + 2) % kNpSlots);                         // unit k+2 (the slot of unit k-1, pooled before T(k))
-      NP_MARK(4);
       k++;
-#ifdef DTC_NP_TRACE
-      n_units++;
-#endif
     }
-#ifdef DTC_NP_TRACE
-    if (lane == 0 && blockIdx.x < 4096) {
-      unsigned long long* o = g_np_trace + (size_t)blockIdx.x * 2 * kNpTraceSlots;
-      for (int i = 0; i < 8; i++) o[i] = tt.acc[i];
-      o[8] = n_units; o[9] = n_items_done; o[10] = n_dma;
-    }
-#endif
     return;
   }
 
@@ -554,16 +497,13 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
   if ((d.flags & 3) == 3) issue_dma(d, 0);
   int k = 0;
   while (true) {
-    NP_MARK(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's share of unit k's DMA has landed (and its output stores)
     __syncthreads();                                       // T: descriptors, tables and the image of unit k are visible
-    NP_MARK(1);
     flush();                                               // the last round of unit k-1
     if (!(d.flags & 1)) break;
     const int ks = k % kNpSlots, kn = ks == kNpSlots - 1 ? 0 : ks + 1;
     const NpU dn = read_desc(kn);                          // unit k+1's window goes in flight now: it lands while unit k is pooled
     if ((dn.flags & 3) == 3) issue_dma(dn, (k + 1) & 1);
-    NP_MARK(2);
     // ---- pool unit k: bins [pa PW, pb PW) in rounds of 28; this wave's four slots are the consecutive bins 28 r + 4 pwv + (0..3)
     const int pa = d.pa, pb = d.pb, staged = (d.flags >> 1) & 1, mode = (d.flags >> 3) & 3, par = (d.flags >> 5) & 3;
     const int buf = k & 1;
@@ -606,7 +546,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
                 const NpRc cy = (rct + (par * 2 + 0) * kNpTabEntries)[2 * ph + iy], cx = (rct + (par * 2 + 1) * kNpTabEntries)[2 * pw + ix];
                 const NpGlb g = *reinterpret_cast<const NpGlb*>(reinterpret_cast<const char*>(ig) + par * 32);
                 const char* gb = reinterpret_cast<const char*>(g.fbase) + q * 16;
-                auto ga = [&](int yy, int xx) { return gb + ((int64_t)yy * g.sh + (int64_t)xx * g.sw) * (int64_t)sizeof(TIn); };
+                auto ga = [&](int yy, int xx) { return gb + ((int64_t)yy * g.sh + (int64_t)xx * g.sw) * (int64_t)sizeof(float); };
                 if (mode == 0) {
                   r1 = *reinterpret_cast<const u32x4*>(ga(cy.lo, cx.lo)); r2 = *reinterpret_cast<const u32x4*>(ga(cy.lo, cx.hi));
                   r3 = *reinterpret_cast<const u32x4*>(ga(cy.hi, cx.lo)); r4 = *reinterpret_cast<const u32x4*>(ga(cy.hi, cx.hi));
@@ -618,7 +558,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
                 }
               }
               float v1[CL], v2[CL], v3[CL], v4[CL];
-              NlLane<TIn>::widen(r1, v1); NlLane<TIn>::widen(r2, v2); NlLane<TIn>::widen(r3, v3); NlLane<TIn>::widen(r4, v4);
+              nl_widen(r1, v1); nl_widen(r2, v2); nl_widen(r3, v3); nl_widen(r4, v4);
               const float w1 = ey.h * ex.h, w2 = ey.h * ex.l, w3 = ey.l * ex.h, w4 = ey.l * ex.l;                     // :95
               // two channels per instruction (v_pk_mul_f32 / v_pk_add_f32: the same IEEE results, half the instructions)
 #pragma unroll
@@ -641,25 +581,11 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
         pend_dst = out + b0 + r0 + 4 * pwv; pend_nv = min(4, nb - (r0 + 4 * pwv));
       }
     }
-    NP_MARK(4);
     d = dn;
     k++;
   }
-#ifdef DTC_NP_TRACE
-  if (tid == 64 && blockIdx.x < 4096) {
-    unsigned long long* o = g_np_trace + (size_t)blockIdx.x * 2 * kNpTraceSlots + kNpTraceSlots;
-    for (int i = 0; i < 8; i++) o[i] = tt.acc[i];
-  }
-#endif
 }
 
-#ifdef DTC_NP_TRACE
-}  // namespace dtc
-extern "C" __attribute__((visibility("default"))) int dtc_debug_np_trace(void* host_dst, size_t bytes) {
-  return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(dtc::g_np_trace), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-namespace dtc {
-#endif
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // Which kernel (measured on MI355X, bench inputs, batch 8, float32 maps; profiles/r04_c_*):
@@ -669,17 +595,14 @@ namespace dtc {
 //                           the pipeline's fixed cost and a quarter of the bin slots busy -- so it is NOT the default there;
 //   > 64 bins (mask head)   the pipelined kernel (two 512-thread workgroups per CU, 78 KB each: two 132-pixel images): 0.129 ms per
 //                           1024-RoI launch against 0.180 for the RoI-stationary LDS kernel (roi_align.hip) that took these before.
-// Float32 output only for the pipelined kernel.  Development / A-B knobs: RoiAlignKnobs::nhwc_* (roi_align_common.h).
-
-template <typename TIn> static int nl_cb() { return 16 * NlLane<TIn>::kCh; }
+// Float32 maps only, and float32 output only for the pipelined kernel.  Development / A-B knobs: RoiAlignKnobs::nhwc_* (roi_align_common.h).
 
 // LDS per workgroup of the pipelined kernel and what it is split into (host side, once per launch)
 struct NpPlan { int lds_b, img_pixels, wgs_per_cu; };
-static bool np_plan(int in_dtype, NpPlan& pl) {
-  const int cb = in_dtype == DTC_F32 ? 64 : 128;
+static bool np_plan(NpPlan& pl) {
   const RoiAlignKnobs& cfg = roi_align_knobs();
   pl.lds_b = (cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 78) * 1024;
-  const int room = pl.lds_b - kNpHdrBytes - kNpPoolWaves * cb * kNpScrPitch * 4;
+  const int room = pl.lds_b - kNpHdrBytes - kNpPoolWaves * kNlCb * kNpScrPitch * 4;
   pl.img_pixels = room < 0 ? 0 : ((room / 2 / kNlChunk) & ~3);       // two images; the DMA writes whole groups of 4 pixels
   if (pl.img_pixels > 8188) pl.img_pixels = 8188;                     // pixel indices stay exact in the float reciprocal
   pl.wgs_per_cu = (160 * 1024) / pl.lds_b;
@@ -689,21 +612,19 @@ static bool np_plan(int in_dtype, NpPlan& pl) {
 }
 static bool np_takes(int bins, int in_dtype, int out_dtype) {
   const RoiAlignKnobs& cfg = roi_align_knobs();
-  return (cfg.nhwc_pipe == 2 || (cfg.nhwc_pipe == 1 && bins > kNlMaxBins)) && out_dtype == DTC_F32 && (in_dtype == DTC_F32 || cfg.nhwc_pipe16);
+  return (cfg.nhwc_pipe == 2 || (cfg.nhwc_pipe == 1 && bins > kNlMaxBins)) && in_dtype == DTC_F32 && out_dtype == DTC_F32;
 }
 
 bool roi_align_nhwc_lds_supported(const RoiAlignParams& p, int in_dtype, int out_dtype) {
   const RoiAlignKnobs& cfg = roi_align_knobs();
   if (!cfg.nhwc_lds || p.sampling_ratio != 2) return false;
-  // 16-bit maps: the direct-gather kernel (8-channel lanes, roi_align.hip) unless asked
-  if (in_dtype != DTC_F32 && !cfg.nhwc_lds_16bit && !cfg.nhwc_pipe16) return false;
+  if (in_dtype != DTC_F32) return false;     // 16-bit maps: the direct-gather kernels (8-channel lanes; roi_align_nhwc16.hip, roi_align.hip)
   const int bins = p.pooled_h * p.pooled_w;
   if (p.pooled_h > 16 || p.pooled_w > 16) return false;
-  const int cb = in_dtype == DTC_F32 ? 64 : 128;
-  if (p.channels % cb != 0) return false;
-  if (np_takes(bins, in_dtype, out_dtype)) { NpPlan pl; if (!np_plan(in_dtype, pl)) return false; }
+  if (p.channels % kNlCb != 0) return false;
+  if (np_takes(bins, in_dtype, out_dtype)) { NpPlan pl; if (!np_plan(pl)) return false; }
   // roi_align_fwd_nhwc_lds: <= 64 bins; the tables and the output slab must leave room for a window image (else: the direct-gather kernel)
-  else if (bins > kNlMaxBins || ((cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 40) * 1024 - (1024 + kNlMaxBins * kNlBinRec + cb * bins * 4)) / kNlChunk < 16 + 3) return false;
+  else if (bins > kNlMaxBins || ((cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 40) * 1024 - (1024 + kNlMaxBins * kNlBinRec + kNlCb * bins * 4)) / kNlChunk < 16 + 3) return false;
   for (int l = 0; l < p.n_levels; l++)
     if (p.lv[l].stride_c != 1 || p.lv[l].height > 65535 || p.lv[l].width > 65535) return false;
   return io_pair_supported(in_dtype, out_dtype);
@@ -718,54 +639,48 @@ static int np_cus() {      // compute units of the device the launch goes to (MI
   return n;
 }
 
-template <typename TIn>
-static int launch_np_t(const RoiAlignParams& p, int in_dtype, hipStream_t stream) {
-  if (raise_lds_once<roi_align_fwd_nhwc_pipe<TIn, true>, roi_align_fwd_nhwc_pipe<TIn, false>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+static int launch_np(const RoiAlignParams& p, hipStream_t stream) {
+  if (raise_lds_once<roi_align_fwd_nhwc_pipe<true>, roi_align_fwd_nhwc_pipe<false>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   NpPlan pl;
-  if (!np_plan(in_dtype, pl)) return DTC_EUNSUPPORTED;
-  const int cb = nl_cb<TIn>();
-  const long long n_items = (long long)p.n_rois * (p.channels / cb);
+  if (!np_plan(pl)) return DTC_EUNSUPPORTED;
+  const long long n_items = (long long)p.n_rois * (p.channels / kNlCb);
   // persistent workgroups: as many as are resident at once (a multiple of the 8 XCDs), fewer when there is less work
   long long per_xcd = (long long)(np_cus() / kXcds) * pl.wgs_per_cu;
   const long long need = (n_items + kXcds - 1) / kXcds;
   if (per_xcd > need) per_xcd = need;
   if (per_xcd < 1) per_xcd = 1;
-  const size_t smem = (size_t)kNpHdrBytes + (size_t)kNpPoolWaves * cb * kNpScrPitch * 4 + 2 * (size_t)pl.img_pixels * kNlChunk;
+  const size_t smem = (size_t)kNpHdrBytes + (size_t)kNpPoolWaves * kNlCb * kNpScrPitch * 4 + 2 * (size_t)pl.img_pixels * kNlChunk;
   if (p.roi_desc)
-    hipLaunchKernelGGL((roi_align_fwd_nhwc_pipe<TIn, true>), dim3((unsigned)(per_xcd * kXcds)), dim3(kNpThreads), smem, stream, p, pl.img_pixels);
+    hipLaunchKernelGGL((roi_align_fwd_nhwc_pipe<true>), dim3((unsigned)(per_xcd * kXcds)), dim3(kNpThreads), smem, stream, p, pl.img_pixels);
   else
-    hipLaunchKernelGGL((roi_align_fwd_nhwc_pipe<TIn, false>), dim3((unsigned)(per_xcd * kXcds)), dim3(kNpThreads), smem, stream, p, pl.img_pixels);
+    hipLaunchKernelGGL((roi_align_fwd_nhwc_pipe<false>), dim3((unsigned)(per_xcd * kXcds)), dim3(kNpThreads), smem, stream, p, pl.img_pixels);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }
 
-template <typename TIn, typename TOut>
+template <typename TOut>
 static int launch_nl_t(const RoiAlignParams& p, hipStream_t stream) {
-  if (raise_lds_once<roi_align_fwd_nhwc_lds<TIn, TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc_lds<TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
   const int bins = p.pooled_h * p.pooled_w;
-  const int cb = nl_cb<TIn>();
-  const int fixed = 1024 + kNlMaxBins * kNlBinRec + cb * bins * 4;
+  const int fixed = 1024 + kNlMaxBins * kNlBinRec + kNlCb * bins * 4;
   const int lds_b = (roi_align_knobs().nhwc_lds_kb ? roi_align_knobs().nhwc_lds_kb : 40) * 1024;
   int img_pixels = ((lds_b - fixed) / kNlChunk) & ~3;           // the DMA writes whole groups of 4 pixels
   if (img_pixels < 16) return DTC_EUNSUPPORTED;
   if (img_pixels > 8188) img_pixels = 8188;                      // pixel indices stay exact in the float reciprocal
-  const int nct = p.channels / cb;
-  hipLaunchKernelGGL((roi_align_fwd_nhwc_lds<TIn, TOut>), dim3((unsigned)p.n_rois * nct), dim3(kNlThreads), fixed + img_pixels * kNlChunk, stream, p, img_pixels);
+  const int nct = p.channels / kNlCb;
+  hipLaunchKernelGGL((roi_align_fwd_nhwc_lds<TOut>), dim3((unsigned)p.n_rois * nct), dim3(kNlThreads), fixed + img_pixels * kNlChunk, stream, p, img_pixels);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }
 
 int launch_roi_align_nhwc_lds(const RoiAlignParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
-  if (np_takes(p.pooled_h * p.pooled_w, in_dtype, out_dtype)) {
-    if (in_dtype == DTC_F32) return launch_np_t<float>(p, in_dtype, stream);
-    if (in_dtype == DTC_F16) return launch_np_t<__half>(p, in_dtype, stream);
-    if (in_dtype == DTC_BF16) return launch_np_t<bf16_t>(p, in_dtype, stream);
-    return DTC_EUNSUPPORTED;
-  }
-  return dispatch_io_pair(in_dtype, out_dtype, [&](auto tin, auto tout) {
-    return launch_nl_t<tag_type<decltype(tin)>, tag_type<decltype(tout)>>(p, stream);
-  });
+  if (in_dtype != DTC_F32) return DTC_EUNSUPPORTED;      // (roi_align_nhwc_lds_supported says so first)
+  if (np_takes(p.pooled_h * p.pooled_w, in_dtype, out_dtype)) return launch_np(p, stream);
+  if (out_dtype == DTC_F32) return launch_nl_t<float>(p, stream);
+  if (out_dtype == DTC_F16) return launch_nl_t<__half>(p, stream);
+  if (out_dtype == DTC_BF16) return launch_nl_t<bf16_t>(p, stream);
+  return DTC_EUNSUPPORTED;
 }
 
 }  // namespace dtc

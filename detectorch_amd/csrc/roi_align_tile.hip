@@ -97,22 +97,6 @@ template <> struct Piece4<bf16_t> {
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// Development aid (-DDTC_TILE_TRACE, tools/r02/trace_tile.py): wave 0's cycle counter at the phase boundaries of a workgroup,
-// accumulated per phase and written to a global table.  Compiled out of the product.
-#ifdef DTC_TILE_TRACE
-constexpr int kTraceSlots = 16;
-__device__ unsigned long long g_tile_trace[kTraceSlots * 16384];
-struct TileTrace {
-  unsigned long long last, acc[kTraceSlots];
-  __device__ __forceinline__ void start() { for (int i = 0; i < kTraceSlots; i++) acc[i] = 0; last = __builtin_readcyclecounter(); }
-  __device__ __forceinline__ void mark(int i) { const unsigned long long n = __builtin_readcyclecounter(); acc[i] += n - last; last = n; }
-};
-#define TT_MARK(i) tt.mark(i)
-#else
-struct TileTrace {};
-#define TT_MARK(i) ((void)0)
-#endif
-
 // element type / slot size of the LDS image: float32 maps -> float32, 16 bytes per (pixel, 4 channels); 16-bit maps -> the raw 16-bit
 // values, 8 bytes per slot (tap = ds_read_b64; simulated on the bench RoIs, tools/r04/lds_taps4.py b64: 5.2 LDS cycles per tap read
 // against 9.6 for ds_read_b128 on a float32 image)
@@ -164,7 +148,7 @@ struct TileGeom {            // one cluster, all uniform
 template <typename TIn, typename TOut, int NT, bool FUSED>
 __device__ __forceinline__ void tile_passes(const RoiAlignParams& p, const dtc_feat_level& L, const TIn* fbase, int c0, int nc,
                                             int bins, float* slab, typename TileLds<TIn>::T* win, const TileRoi* troi, const TileGeom& g,
-                                            const TileItem& it, int rl, int bin, TileTrace& tt) {
+                                            const TileItem& it, int rl, int bin) {
   constexpr int NW = NT / 64;
   constexpr int U = TileShape<NT>::kUnits;
   typedef typename TileLds<TIn>::T TL;
@@ -304,72 +288,6 @@ __device__ __forceinline__ void tile_passes(const RoiAlignParams& p, const dtc_f
     }
   };
 
-#ifdef DTC_TILE_REPLAY
-  // Development aid (tools/r06/replay.sh, round 6: VERDICT r05 item 5): the shipped launch's exact work order with only ONE of its
-  // three streams left in -- same workgroups, same clusters, same passes, same addresses.  Compiled out of the product.
-  //   1  staging loads only (no LDS commit, no pooling, no stores, no barriers): the loads are consumed by an XOR that is never stored
-  //   4  loads + commit + the two barriers per pass (no pooling, no stores)
-  //   2  pooled-slab stores only (the slab holds whatever LDS held; no loads, no commit, no pooling, no barriers)
-  //   3  pooling only, from the LDS image as it is (no loads, no commit, no stores; both barriers per pass)
-  {
-    uint32_t sink = 0;
-    if (DTC_TILE_REPLAY == 1 || DTC_TILE_REPLAY == 4) { if (vec) issue(0); }
-    int cs_prev = 0, nq_prev = 0;
-#pragma unroll 1
-    for (int qs = 0; qs < nq_tot; qs += nq_pass) {
-      const int cs = 4 * qs;
-      const int nq_cur = min(nq_pass, nq_tot - qs);
-      if (DTC_TILE_REPLAY == 1) {
-#pragma unroll
-        for (int u = 0; u < U; u++) { if constexpr (L16) sink ^= v[u].x ^ v[u].y; else sink ^= __float_as_uint(v[u].x) ^ __float_as_uint(v[u].w); }
-        if (vec && qs + nq_pass < nq_tot) issue(cs + 4 * nq_pass);
-      } else if (DTC_TILE_REPLAY == 4) {
-        if (vec) commit(); else stage_scalar(cs);
-        __syncthreads();
-        if (vec && qs + nq_pass < nq_tot) issue(cs + 4 * nq_pass);
-        __syncthreads();
-      } else if (DTC_TILE_REPLAY == 2) {
-        store_slab(cs, nq_cur);
-      } else if (DTC_TILE_REPLAY == 3) {
-        __syncthreads();
-        if (it.on) {
-          float* so = slab + rl * (4 * nq_cur * bins) + bin;
-#pragma unroll 1
-          for (int q = 0; q < nq_cur; q++) {
-            const char* wq = reinterpret_cast<const char*>(win) + uni(q * plane * SB);
-            f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
-#pragma unroll
-            for (int iy = 0; iy < 2; iy++) {
-              if constexpr (!L16) {
-                f32x4 t[2][4];
-#pragma unroll
-                for (int ix = 0; ix < 2; ix++)
-#pragma unroll
-                  for (int k = 0; k < 4; k++) t[ix][k] = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(wq + it.a[iy][ix][k], 16));
-#pragma unroll
-                for (int ix = 0; ix < 2; ix++) {
-                  const float w1 = it.yh[iy] * it.xh[ix], w2 = it.yh[iy] * it.xl[ix], w3 = it.yl[iy] * it.xh[ix], w4 = it.yl[iy] * it.xl[ix];
-                  a01 += w1 * t[ix][0].lo + w2 * t[ix][1].lo + w3 * t[ix][2].lo + w4 * t[ix][3].lo;
-                  a23 += w1 * t[ix][0].hi + w2 * t[ix][1].hi + w3 * t[ix][2].hi + w4 * t[ix][3].hi;
-                }
-              }
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            float* o = so + uni(4 * q * bins);
-            o[0] = a01.x * 0.25f; o[bins] = a01.y * 0.25f; o[2 * bins] = a23.x * 0.25f; o[3 * bins] = a23.y * 0.25f;
-          }
-        }
-        __syncthreads();
-      }
-      cs_prev = cs; nq_prev = nq_cur;
-    }
-    (void)cs_prev; (void)nq_prev;
-    if (sink == 0x9e3779b9u && p.n_rois < 0) reinterpret_cast<uint32_t*>(p.out)[0] = sink;     // never true: keeps the loads alive
-  }
-  TT_MARK(10);
-}
-#else
-  TT_MARK(3);
   if (vec) issue(0);
   int cs_prev = 0, nq_prev = 0;
 #pragma unroll 1
@@ -377,13 +295,9 @@ __device__ __forceinline__ void tile_passes(const RoiAlignParams& p, const dtc_f
     const int cs = 4 * qs;
     const int nq_cur = min(nq_pass, nq_tot - qs);
     if (vec) commit(); else stage_scalar(cs);
-    TT_MARK(4);
     if (nq_prev) store_slab(cs_prev, nq_prev);
-    TT_MARK(5);
     __syncthreads();
-    TT_MARK(6);
     if (vec && qs + nq_pass < nq_tot) issue(cs + 4 * nq_pass);    // next pass: in flight (registers) while this one is pooled
-    TT_MARK(7);
     if (it.on) {
       float* so = slab + rl * (4 * nq_cur * bins) + bin;
 #pragma unroll 1
@@ -455,16 +369,11 @@ __device__ __forceinline__ void tile_passes(const RoiAlignParams& p, const dtc_f
         o[0] = a0 * 0.25f; o[bins] = a1 * 0.25f; o[2 * bins] = a2 * 0.25f; o[3 * bins] = a3 * 0.25f;
       }
     }
-    TT_MARK(8);
     __syncthreads();
-    TT_MARK(9);
     cs_prev = cs; nq_prev = nq_cur;
   }
   if (nq_prev) store_slab(cs_prev, nq_prev);   // the next cluster writes the slab only behind its own first barrier
-  TT_MARK(10);
 }
-#endif
-
 
 // Work item of block b: XCD x (= b % 8) owns a contiguous slice of the (cluster group, channel block) items, as in
 // xcd_work_item, but walks it BACK TO FRONT: the visiting order ends with the coarsest level of an image, whose RoIs have the
@@ -495,7 +404,7 @@ __global__ __launch_bounds__(NT, (TileBounds<TIn, NT>::kWaves)) void roi_align_f
   constexpr int kMaxPos = TileShape<NT>::kUnits * NW * 16;                  // 16-byte pieces the register pipeline can carry per quad
   const int tid = threadIdx.x;
   const int nct = ceil_div(p.channels, p.ch_block);
-  int wi = tile_work_item(blockIdx.x, gridDim.x, reverse);
+  const int wi = tile_work_item(blockIdx.x, gridDim.x, reverse);
   int grp = wi / nct;
   int c0 = (wi - grp * nct) * p.ch_block;
   {
@@ -509,17 +418,11 @@ __global__ __launch_bounds__(NT, (TileBounds<TIn, NT>::kWaves)) void roi_align_f
       const int cbi = j / ngx, gl = j - cbi * ngx;
       grp = x * ngx + ((reverse & 1) ? ngx - 1 - gl : gl);
       c0 = cbi * p.ch_block;
-      wi = grp * nct + cbi;
     }
   }
   const int nc = min(p.ch_block, p.channels - c0);
   const int bins = p.pooled_h * p.pooled_w;
   const int K = kgroup;
-  TileTrace tt;
-#ifdef DTC_TILE_TRACE
-  tt.start();
-  const unsigned long long wall0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---- A + B (wavefront 0). A: lane k forms the window of RoI k.  B: greedy clustering along the visiting order, by the whole
   // wave on the register copies (readlane with a uniform index: no LDS round trips, no barrier between A and B) ------------
@@ -588,8 +491,6 @@ __global__ __launch_bounds__(NT, (TileBounds<TIn, NT>::kWaves)) void roi_align_f
     if (tid == 0) *ngp = ng;
   }
   __syncthreads();
-  TT_MARK(0);
-  TT_MARK(1);
 
   // ---- C. clusters ----------------------------------------------------------------------------------------------------
   const int ngroups = uni(*ngp);
@@ -677,27 +578,9 @@ __global__ __launch_bounds__(NT, (TileBounds<TIn, NT>::kWaves)) void roi_align_f
         asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));   // one finished VGPR per tap: do not re-derive in the loop
         it.a[iy][ix][0] = t0; it.a[iy][ix][1] = t1; it.a[iy][ix][2] = t2; it.a[iy][ix][3] = t3;
       }
-    TT_MARK(2);
-    tile_passes<TIn, TOut, NT, FUSED>(p, L, fbase, c0, nc, bins, slab, win, troi, g, it, rl, bin, tt);
+    tile_passes<TIn, TOut, NT, FUSED>(p, L, fbase, c0, nc, bins, slab, win, troi, g, it, rl, bin);
   }
-#ifdef DTC_TILE_TRACE
-  if (tid == 0 && blockIdx.x < 16384) {
-    unsigned long long* o = g_tile_trace + (size_t)blockIdx.x * kTraceSlots;
-    for (int i = 0; i < 11; i++) o[i] = tt.acc[i];
-    o[11] = wall0; o[12] = __builtin_amdgcn_s_memrealtime();
-    o[13] = (unsigned long long)ngroups; o[14] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
-    o[15] = (unsigned long long)wi;
-  }
-#endif
 }
-
-#ifdef DTC_TILE_TRACE
-}  // namespace dtc
-extern "C" __attribute__((visibility("default"))) int dtc_debug_tile_trace(void* host_dst, size_t bytes) {
-  return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(dtc::g_tile_trace), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-namespace dtc {
-#endif
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // launch shape that no knob changes (the knobs: RoiAlignKnobs::tile_*, roi_align_common.h)

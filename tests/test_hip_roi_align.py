@@ -523,8 +523,8 @@ def test_nhwc16_grouped_kernel_padding_rows_tail_groups_and_far_levels(hip, orac
 def test_nhwc_lds_dma_kernel_vs_oracle(hip, oracle, dtype, C):
     """channels_last feature maps, 7x7 bins, sampling ratio 2: window staged with LDS-DMA, lane <-> channel chunk.  Small boxes
     (one strip), large ones (several strips of bin rows), boxes no strip fits (per-bin-row straight from global), every border case,
-    the 42-column P5 map; float32 maps take the new kernel, 16-bit maps the direct-gather kernel by default (the new one in the
-    child-process test below): bit-exact against the oracle on the up-cast maps, and the 16-bit outputs are that result rounded once."""
+    the 42-column P5 map; float32 maps take the new kernel, 16-bit maps the direct-gather kernels: bit-exact against the oracle on
+    the up-cast maps, and the 16-bit outputs are that result rounded once."""
     feats, rois5, lv = _nhwc_case(oracle, C, C + len(dtype))
     tdt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype]
     tf = [cu(f).to(tdt).contiguous(memory_format=torch.channels_last) for f in feats]
@@ -551,8 +551,7 @@ sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "oracle")); sys.
 import oracle as orc
 from detectorch_amd import hip, synth
 import test_hip_roi_align as T
-sixteen = (os.environ.get("DTC_RA_NHWC_LDS_16BIT") or os.environ.get("DTC_RA_NHWC_PIPE16")
-           or ("DTC_RA_NHWC16" in os.environ and "DTC_RA_NHWC_DIRECT32" not in os.environ))
+sixteen = "DTC_RA_NHWC16" in os.environ and "DTC_RA_NHWC_DIRECT32" not in os.environ
 for ph in (7, 14):
     for tdt, C in ((torch.float32, 64),) + (((torch.float16, 128), (torch.bfloat16, 256)) if sixteen else ()):
         feats, rois5, lv = T._nhwc_case(orc, C, 5 + ph, R=260 if ph == 7 else 120)
@@ -580,15 +579,13 @@ _D0 = "DTC_RA_NHWC_DIRECT32=0 DTC_RA_NHWC16=0 "        # float32 and 16-bit maps
 
 
 @pytest.mark.parametrize("env", [_D0 + "DTC_RA_NHWC_LDS_KB=24", _D0 + "DTC_RA_NHWC_LDS_KB=78", _D0 + "DTC_RA_NHWC_LDS_KB=156", _D0 + "DTC_RA_NHWC_LDS=0",
-                                 _D0 + "DTC_RA_NHWC_LDS_16BIT=1", _D0 + "DTC_RA_NHWC_LDS_16BIT=1 DTC_RA_NHWC_LDS_KB=24",
                                  _D0 + "DTC_RA_NHWC_PIPE=2", _D0 + "DTC_RA_NHWC_PIPE=2 DTC_RA_NHWC_LDS_KB=30", _D0 + "DTC_RA_NHWC_PIPE=2 DTC_RA_NHWC_LDS_KB=156",
-                                 _D0 + "DTC_RA_NHWC_PIPE=2 DTC_RA_NHWC_PIPE16=1", _D0 + "DTC_RA_NHWC_PIPE=2 DTC_RA_NHWC_PIPE16=1 DTC_RA_NHWC_LDS_KB=40",
                                  _D0 + "DTC_RA_NHWC_PIPE=0", "DTC_RA_NHWC16=0", "DTC_RA_NHWC_DIRECT32=0", "DTC_RA_NHWC16=1"])
 def test_nhwc_lds_image_sizes_in_child_process(hip, oracle, env):
     """The LDS image size decides how many strips a window takes (24 KB: nearly every RoI in several strips or straight from
     global; 156 KB: one workgroup per CU, one strip) -- and must not change a bit; DTC_RA_NHWC_LDS=0 is the direct-gather kernel.
     DTC_RA_NHWC_PIPE=2: the pipelined kernel (round 4) for 7 x 7 bins too (by default it takes the 14 x 14 launches only), at
-    image sizes from a handful of pixels to one workgroup per CU, float32 and 16-bit maps; =0: the round-3 kernels everywhere.
+    image sizes from a handful of pixels to one workgroup per CU (float32 maps: the only ones the LDS-DMA kernels take); =0: the round-3 kernels everywhere.
     DTC_RA_NHWC16=0: 16-bit maps through the one-RoI-per-workgroup direct kernel instead of the grouped one (roi_align_nhwc16.hip).
     DTC_RA_NHWC_DIRECT32=0: float32 maps with <= 64 bins on the LDS-DMA kernels instead of the grouped direct kernel (4-channel lanes);
     the LDS-kernel settings above carry both switches so that they reach the kernels they size.  DTC_RA_NHWC16=1: the defaults, 16-bit maps included.

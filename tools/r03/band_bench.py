@@ -2,7 +2,6 @@
 kernel on the same descriptors -- bit-exact comparison, launch times (HIP events), band item statistics.
     python tools/r03/band_bench.py [--batch 8] [--iters 30] [--workload cfg3|hard]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -76,17 +75,6 @@ def main():
                                            p.out_code, hip.stream_ptr(dev))
         ref = paths[0].mask_feats.clone(); mask_ws(0); torch.cuda.synchronize()
         print("%s mask head: workspace entry == packed entry: %s ; %.4f ms vs %.4f ms" % (a.tag, bool(torch.equal(ref, paths[0].mask_feats)), t(mask_ws), t(mask_packed)))
-    if hasattr(L, "dtc_debug_band_trace"):          # the development build (tools/r03/build_trace_lib.sh): cycles per phase
-        buf = (ctypes.c_ulonglong * 16)()
-        L.dtc_debug_band_trace(buf, 1)
-        band(0)
-        torch.cuda.synchronize()
-        L.dtc_debug_band_trace(buf, 1)
-        names = ["unit fetch", "first batch (issue+commit)", "set-up", "issue", "pool", "wait B1", "commit", "slab store", "wait B2"]
-        tot = float(sum(buf[:9])) or 1.0
-        print("phase trace of one launch (thread 0 of every workgroup, shader cycles summed over %d workgroups): total %.1f M" % (256, tot / 1e6))
-        for i, nm in enumerate(names):
-            print("   %-28s %8.2f M  %5.1f %%" % (nm, buf[i] / 1e6, 100.0 * buf[i] / tot))
     alg = paths[0].box_roialign_bytes()
     print("%s band entry (prep kernels + sweep) %.4f ms = %.2f TB/s (frac %.3f) | cluster kernel %.4f ms (frac %.3f) | env %s"
           % (a.tag, tb, alg / tb / 1e9, alg / tb / 1e9 / 8.0, tc, alg / tc / 1e9 / 8.0,

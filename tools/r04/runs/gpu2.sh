@@ -1,4 +1,5 @@
 #!/bin/bash
+# (the steps of this run that used builds or knobs removed since are cut: git show 7c22f5a:tools/r04/runs/gpu2.sh)
 # Round 4, set 2: the pipelined channels_last RoIAlign kernel -- parity tests, then A/B against the round-3 kernel and an LDS sweep.
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
@@ -18,14 +19,9 @@ t "pipe 53 KB, 2 WG/CU launched" "DTC_RA_NHWC_WGS=2" ""
 t "pipe 53 KB, 4 launched (oversubscribed)" "DTC_RA_NHWC_WGS=4" ""
 t "pipe 53 KB, no XCD slices" "DTC_RA_NO_XCD=1" ""
 t "fp16 direct (shipped)" "DTC_X=0" "--fp16"
-t "fp16 pipe 78 KB" "DTC_RA_NHWC_PIPE16=1" "--fp16"
-t "fp16 pipe 53 KB" "DTC_RA_NHWC_PIPE16=1 DTC_RA_NHWC_LDS_KB=53" "--fp16"
-t "fp16 pipe 104 KB" "DTC_RA_NHWC_PIPE16=1 DTC_RA_NHWC_LDS_KB=104" "--fp16"
 t "fp16 cfg5 (2000 rois) direct" "DTC_X=0" "--fp16 --top-n 2000"
-t "fp16 cfg5 (2000 rois) pipe 78" "DTC_RA_NHWC_PIPE16=1" "--fp16 --top-n 2000"
 t "mask fp32 old path" "DTC_RA_NHWC_PIPE=0" "--mask"
 t "mask fp32 pipe" "DTC_X=0" "--mask"
 t "mask fp16 direct" "DTC_X=0" "--mask --fp16"
-t "mask fp16 pipe" "DTC_RA_NHWC_PIPE16=1" "--mask --fp16"
 echo -n "NCHW shipped (same box) | "; timeout 120 $BOX 2>&1 | tail -1
 } 2>&1 | tee $O/ab.log
