@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
       if (m == 0ull) continue;                                 // uniform per wave
       int base = 0;
       if (lane == 0) base = atomicAdd(&running, __builtin_popcountll(m));
-      base = __builtin_amdgcn_readfirstlane(base);
+      base = uni(base);
       if (ok) {
         qs[r] = s;
         keys[base + lanes_below(m, lane)] = make_desc_key(s, (uint32_t)r);
@@ -862,7 +862,7 @@ static int postprocess_detections(const DetCall& c) {
   hipLaunchKernelGGL(det_candidates_kernel, dim3(n_cls - 1, batch), dim3(kDetThreads), smem, s, p);
   DTC_CHECK_LAUNCH();
   if (soft) {
-    if (raise_lds_once<det_soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+    if (raise_lds_once<det_soft_nms_kernel>() != DTC_OK) return DTC_ELAUNCH;
     hipLaunchKernelGGL(det_soft_nms_kernel, dim3(n_cls - 1, batch), dim3(64), soft_nms_lds_bytes(max_rois), s, p, c.opt->soft_sigma,
                        c.nms_thresh, c.opt->soft_score_thresh, mode.soft);
     DTC_CHECK_LAUNCH();

@@ -29,10 +29,13 @@
 
 namespace dtc {
 
+constexpr int kCuLdsBytes = 160 * 1024;      // the LDS of a CU (gfx950): the most one workgroup can have, static + dynamic
+
 // Raise the dynamic-LDS limit of one or more kernels (instantiations of kernel templates included) once per process: thread-safe
 // (std::call_once), stops at the first failure, and the status is remembered, so every caller of a failed raise gets DTC_ELAUNCH.
+// The default lifts the limit all the way; a kernel with static LDS of its own names what is left.
 template <auto... Kernels>
-inline int raise_lds_once(int bytes) {
+inline int raise_lds_once(int bytes = kCuLdsBytes) {
   static std::once_flag once;
   static hipError_t rc = hipSuccess;
   std::call_once(once, [bytes] {
@@ -81,6 +84,10 @@ template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) {
 __device__ __forceinline__ float4 bf16x4_to_f32(uint2 r) {
   return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
                      __uint_as_float(r.y & 0xffff0000u));
+}
+__device__ __forceinline__ float4 f16x4_to_f32(uint2 r) {
+  const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
+  return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
 }
 
 // Streaming (non-temporal, `nt`) stores for outputs that are written once and never re-read by the kernel that writes them: the pooled

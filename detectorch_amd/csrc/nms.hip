@@ -245,8 +245,7 @@ __global__ __launch_bounds__(64) void nms_reduce_kernel(const uint64_t* __restri
     const int left = n - rb * 64;
     const uint64_t valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
     uint64_t cand = valid & ~removed[rb];
-    cand = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(cand >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cand);   // uniform by construction: keep it in SGPRs
+    cand = uni(cand);   // uniform by construction
     // In-block greedy resolve as a fixed point: row i is kept iff it is a candidate and no KEPT earlier row of the block
     // suppresses it.  F(K) = {i in cand : (suppressors(i) & K) == 0} is antitone and the greedy answer is its unique fixed
     // point; iterating from K = cand fixes the i-th candidate after at most i steps (typically 2-4 wave-wide steps in all,
@@ -384,8 +383,7 @@ __global__ __launch_bounds__(kReduceLdsThreads) void nms_reduce_lds_kernel(const
     const int left = n - rb * 64;
     const uint64_t valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
     uint64_t cand = valid & ~removed[rb];
-    cand = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(cand >> 32)) << 32) |
-           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cand);   // uniform by construction: keep it in SGPRs
+    cand = uni(cand);   // uniform by construction
     // in-block greedy resolve as a fixed point (see nms_reduce_kernel)
     uint64_t keepw = cand;
     if (cand != 0) {
@@ -562,7 +560,7 @@ DTC_API int dtc_segment_sort_desc(const float* scores, int score_stride_elems, c
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t smem = (size_t)dtc::next_pow2(n_stride) * sizeof(uint64_t);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    if (dtc::raise_lds_once<dtc::segment_sort_desc_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+    if (dtc::raise_lds_once<dtc::segment_sort_desc_kernel>() != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::segment_sort_desc_kernel, dim3(n_seg), dim3(dtc::kSortThreads), smem, s, scores,
                      score_stride_elems, boxes, box_stride_elems, counts, n_stride, order, sorted_boxes, sorted_scores);
@@ -594,7 +592,7 @@ DTC_API int dtc_nms(const float* dets, int n, float thresh, void* workspace, siz
   if (rc != DTC_OK) return rc;
   const size_t smem = (size_t)dtc::next_pow2(n) * sizeof(uint64_t);
   if (smem > 32 * 1024) {   // static __shared__ of the kernel comes on top: raise the limit well before dynamic + static reaches 64 KB
-    if (dtc::raise_lds_once<dtc::nms_finalize_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+    if (dtc::raise_lds_once<dtc::nms_finalize_kernel>() != DTC_OK) return DTC_ELAUNCH;
   }
   hipLaunchKernelGGL(dtc::nms_finalize_kernel, dim3(1), dim3(dtc::kSortThreads), smem, s, keep, cnt, order, keep_out, keep_count);
   DTC_CHECK_LAUNCH();
@@ -642,7 +640,7 @@ DTC_API int dtc_soft_nms(const float* dets, int n, float sigma, float overlap_th
   if (n > 6000) return DTC_EUNSUPPORTED;
   if (!dets || !dets_out || !inds_out) return DTC_EINVAL;
   const size_t smem = dtc::soft_nms_lds_bytes(n);
-  if (dtc::raise_lds_once<dtc::soft_nms_kernel>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (dtc::raise_lds_once<dtc::soft_nms_kernel>() != DTC_OK) return DTC_ELAUNCH;
   hipLaunchKernelGGL(dtc::soft_nms_kernel, dim3(1), dim3(64), smem, s, dets, n, sigma, overlap_thresh, score_thresh, method,
                      dets_out, inds_out, n_out);
   DTC_CHECK_LAUNCH();

@@ -40,12 +40,6 @@ constexpr int kRoiAlignThreads = 256;
 constexpr int kMaxTableEntries = 2048;  // PH*gh + PW*gw ; larger (adaptive sampling on a huge RoI) -> on-the-fly path
 
 // ---- what the kernels of this file share ----------------------------------------------------------------------------------
-// padding row of a fixed-shape batch (fpn.hip emits level -1): defined output
-template <typename TOut>
-__device__ __forceinline__ void zero_outputs(TOut* out, int n) {
-  for (int o = threadIdx.x; o < n; o += kRoiAlignThreads) out[o] = from_f32<TOut>(0.f);
-}
-
 // The two per-axis tables of a RoI, one behind the other: ytab[ph * gh + iy] = tab[..], xtab[pw * gw + ix] = tab[ny + ..]; lo / hi
 // multiplied by (ymul, xmul) -- 1: element indices along the axis, the element strides: offsets inside the image.
 __device__ __forceinline__ void build_axis_tables(AxisEntry* tab, const RoiHead& hd, const dtc_feat_level& L, int ny, int nx,
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_general(RoiAli
   const int bins = p.pooled_h * p.pooled_w;
   const RoiHead hd = load_roi_head(p, blockIdx.x);
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)hd.r * p.channels + c0) * bins;
-  if (hd.lvl < 0 || hd.lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
+  if (hd.lvl < 0 || hd.lvl >= p.n_levels) { zero_outputs<TOut, kRoiAlignThreads>(out, nc * bins, threadIdx.x); return; }
   const dtc_feat_level L = p.lv[hd.lvl];
   const int ny = p.pooled_h * hd.gh, nx = p.pooled_w * hd.gw;
   AxisEntry* xtab = ytab + ny;
@@ -215,15 +209,6 @@ struct StagerNCHW {
     }
   }
 };
-
-// four consecutive channels of a channels_last pixel as float32: one 16-byte (float32) / 8-byte (16-bit) load
-__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 load4(const __half* p) {
-  const uint2 r = *reinterpret_cast<const uint2*>(p);
-  const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
-  return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
-}
-__device__ __forceinline__ float4 load4(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
 
 template <typename TIn>
 struct StagerNHWC {
@@ -389,7 +374,7 @@ __global__ __launch_bounds__(kRoiAlignThreads, kLdsKernelWaves) void roi_align_f
   const RoiHead hd = load_roi_head(p, ri);
   const int r = hd.r, lvl = hd.lvl, b = hd.b;
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins;
-  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
+  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs<TOut, kRoiAlignThreads>(out, nc * bins, tid); return; }
   const dtc_feat_level L = p.lv[lvl];
   const float sh = hd.sh, bin_h = hd.bin_h, count = hd.count;
   const int gh = hd.gh, gw = hd.gw;
@@ -543,7 +528,7 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
   const RoiHead hd = load_roi_head(p, ri);
   const int r = hd.r, lvl = hd.lvl, b = hd.b;
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)r * p.channels + c0) * bins;
-  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs(out, nc * bins); return; }
+  if (lvl < 0 || lvl >= p.n_levels) { zero_outputs<TOut, kRoiAlignThreads>(out, nc * bins, tid); return; }
   const dtc_feat_level L = p.lv[lvl];
   const float sw = hd.sw, sh = hd.sh, bin_h = hd.bin_h, bin_w = hd.bin_w, count = hd.count, inv_count = hd.inv_count;
   const int gh = hd.gh, gw = hd.gw;
@@ -564,7 +549,7 @@ __global__ __launch_bounds__(kRoiAlignThreads) void roi_align_fwd_nhwc(RoiAlignP
       constexpr int NQ8 = CB / 8;
       const int q8 = tid % NQ8, slot8 = tid / NQ8;
       // one scalar base for the workgroup, 32-bit byte offsets per lane (global_load ... saddr): a tap costs one v_add
-      const int bu = __builtin_amdgcn_readfirstlane(b);
+      const int bu = uni(b);
       const char* ubase = reinterpret_cast<const char*>(reinterpret_cast<const TIn*>(L.data) + (int64_t)bu * L.stride_n + c0);
       const uint32_t lane_off = 16u * (uint32_t)q8;
       auto ld = [&](uint32_t yo, uint32_t xo) { return *reinterpret_cast<const uint4*>(ubase + (yo + xo)); };
@@ -726,7 +711,7 @@ constexpr int kLdsKernelBytes = 52 * 1024;   // dynamic LDS of a roi_align_fwd_l
 template <typename TIn, typename TOut, int CB>
 static int launch_nhwc_cb(const RoiAlignParams& p, hipStream_t stream) {
   const size_t smem = (size_t)kLdsTableFloats * 4 + (size_t)CB * p.pooled_h * p.pooled_w * 4 + 16;
-  if (raise_lds_once<roi_align_fwd_nhwc<TIn, TOut, CB>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc<TIn, TOut, CB>>() != DTC_OK) return DTC_ELAUNCH;
   const int nct = ceil_div(p.channels, CB);
   hipLaunchKernelGGL((roi_align_fwd_nhwc<TIn, TOut, CB>), dim3((unsigned)p.n_rois * nct), dim3(kRoiAlignThreads), smem, stream, p);
   DTC_CHECK_LAUNCH();
@@ -748,7 +733,7 @@ static int launch_nhwc(const RoiAlignParams& p, hipStream_t stream) {
 template <typename TIn, typename TOut>
 static int launch_lds(const RoiAlignParams& p, hipStream_t stream) {
   if (p.n_rois == 0) return DTC_OK;
-  if (raise_lds_once<roi_align_fwd_lds<TIn, TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_lds<TIn, TOut>>() != DTC_OK) return DTC_ELAUNCH;
   const int nct = ceil_div(p.channels, p.ch_block);
   hipLaunchKernelGGL((roi_align_fwd_lds<TIn, TOut>), dim3((unsigned)p.n_rois * nct), dim3(kRoiAlignThreads), kLdsKernelBytes, stream, p,
                      kLdsKernelBytes / 4);

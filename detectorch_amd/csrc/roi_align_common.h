@@ -1,9 +1,11 @@
-// What the RoIAlign kernels (roi_align*.hip) share.  Device side: launch parameters, the XCD-aware work assignment, and the
+// What the RoIAlign kernels (roi_align*.hip) share.  Device side: launch parameters, the XCD-aware work assignment, the four-element
+// load / store and the zero fill, and the
 // RoI geometry of roi_align_forward_loop (lib/cppcuda_cffi/src/cpp/roi_align_cpu_loop.cpp:36-173) restated operation for
 // operation so that every kernel forms bit-identical sampling positions and weights.  Host side: the (input, output) dtype
 // dispatch, the A/B knob table and the launchers' declarations.
 #pragma once
 #include "dtc_common.h"
+#include "wave_ops.h"
 
 namespace dtc {
 
@@ -146,6 +148,31 @@ template <> __device__ __forceinline__ void fma_pair16<bf16_t>(f32x2& acc, uint3
   acc = __builtin_elementwise_fma(v, w2, acc);
 }
 template <> __device__ __forceinline__ void fma_pair16<float>(f32x2&, uint32_t, float) {}   // never instantiated for float maps
+
+// Four consecutive elements of a map as float32: one 16-byte (float32) / 8-byte (16-bit) load.
+__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 load4(const __half* p) { return f16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
+__device__ __forceinline__ float4 load4(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
+
+// Four consecutive outputs as TOut, rounded as from_f32 rounds each, in one streaming store (why streaming: dtc_common.h).
+template <typename TOut> __device__ __forceinline__ void store4(TOut* d, float4 v);
+template <> __device__ __forceinline__ void store4<float>(float* d, float4 v) { store_stream16(d, v); }
+template <> __device__ __forceinline__ void store4<__half>(__half* d, float4 v) {
+  const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
+  store_stream8(d, *reinterpret_cast<const uint32_t*>(&a), *reinterpret_cast<const uint32_t*>(&b));
+}
+template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* d, float4 v) {
+  store_stream8(d, (uint32_t)from_f32<bf16_t>(v.x).bits | ((uint32_t)from_f32<bf16_t>(v.y).bits << 16),
+                (uint32_t)from_f32<bf16_t>(v.z).bits | ((uint32_t)from_f32<bf16_t>(v.w).bits << 16));
+}
+
+// Padding row of a fixed-shape batch (fpn.hip emits level -1): defined output.  THREADS threads (a workgroup, or the 64 lanes of a
+// wave) clear n outputs; tid: the thread's index among them.  (roi_align_fwd_map keeps a loop of its own: with the call its
+// prepared instantiations came out with another branch layout, profiles/README.md "RoIAlign device primitives".)
+template <typename TOut, int THREADS>
+__device__ __forceinline__ void zero_outputs(TOut* out, int n, int tid) {
+  for (int o = tid; o < n; o += THREADS) out[o] = from_f32<TOut>(0.f);
+}
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 // The (input, output) dtype pairs RoIAlign serves: float32 accumulation always, float32 or the map's own 16-bit type out, and a

@@ -32,32 +32,7 @@ int roi_align_get_exact();
 
 constexpr int kMapThreads = 1024;
 constexpr int kMapWaves = kMapThreads / 64;
-constexpr int kMapLdsBytes = 160 * 1024 - 512;      // dynamic LDS budget (static: the rendezvous arrays)
-
-
-template <typename TOut> __device__ __forceinline__ void map_store4(TOut* d, float4 v);
-template <> __device__ __forceinline__ void map_store4<float>(float* d, float4 v) { store_stream16(d, v); }     // streaming stores: dtc_common.h
-template <> __device__ __forceinline__ void map_store4<__half>(__half* d, float4 v) {
-  const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-  store_stream8(d, *reinterpret_cast<const uint32_t*>(&a), *reinterpret_cast<const uint32_t*>(&b));
-}
-template <> __device__ __forceinline__ void map_store4<bf16_t>(bf16_t* d, float4 v) {
-  store_stream8(d, (uint32_t)from_f32<bf16_t>(v.x).bits | ((uint32_t)from_f32<bf16_t>(v.y).bits << 16),
-                (uint32_t)from_f32<bf16_t>(v.z).bits | ((uint32_t)from_f32<bf16_t>(v.w).bits << 16));
-}
-
-template <typename TIn> struct MapLoad4;
-template <> struct MapLoad4<float> { static __device__ __forceinline__ float4 ld(const float* p) { return *reinterpret_cast<const float4*>(p); } };
-template <> struct MapLoad4<__half> {
-  static __device__ __forceinline__ float4 ld(const __half* p) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    const __half2 a = *reinterpret_cast<const __half2*>(&r.x), b = *reinterpret_cast<const __half2*>(&r.y);
-    return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
-  }
-};
-template <> struct MapLoad4<bf16_t> {
-  static __device__ __forceinline__ float4 ld(const bf16_t* p) { return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p)); }
-};
+constexpr int kMapLdsBytes = kCuLdsBytes - 512;      // dynamic LDS budget (static: the rendezvous arrays)
 
 // One sample of one bin: 4 taps x NQ channel quads.  ylo / yhi: byte offsets of the two rows, xlo / xhi of the two columns.
 template <int NQ>
@@ -75,8 +50,6 @@ __device__ __forceinline__ void map_sample(const char* map, int plane_bytes, int
     acc[q][1] += w1 * v1.hi + w2 * v2.hi + w3 * v3.hi + w4 * v4.hi;
   }
 }
-
-__device__ __forceinline__ int map_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Per-RoI record of the per-launch preparation pass (map_prep_kernel): everything about a RoI that does not depend on the
 // channels -- which each of the C / 8 channel-group workgroups used to re-derive (two IEEE divisions for the bin sizes, two
@@ -229,7 +202,7 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
       if (ri < 0) {                            // nothing held: take a RoI and fetch its record
         int t = 0;
         if (lane == 0) t = atomicAdd(&s_next, 1);
-        ri = map_uni(t);
+        ri = uni(t);
         if (ri < r_end) fetch(ri, rec);
       }
       if (ri >= r_end) break;
@@ -249,9 +222,9 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
       } else {
         const RoiHead hd = roi_head_from_raw(p, rec.raw);
         hr = hd.r; hb = hd.b; padrow = hd.lvl < 0 || hd.lvl >= p.n_levels;
-        gh = map_uni(hd.gh); gw = map_uni(hd.gw);
-        sh = __uint_as_float(map_uni(__float_as_uint(hd.sh))); sw = __uint_as_float(map_uni(__float_as_uint(hd.sw)));
-        bin_h = __uint_as_float(map_uni(__float_as_uint(hd.bin_h))); bin_w = __uint_as_float(map_uni(__float_as_uint(hd.bin_w)));
+        gh = uni(hd.gh); gw = uni(hd.gw);
+        sh = uni(hd.sh); sw = uni(hd.sw);
+        bin_h = uni(hd.bin_h); bin_w = uni(hd.bin_w);
         inv_count = hd.inv_count; count = hd.count;
         rcp_count = 1.0 / (double)count;
         // more than 64 entries per axis (a RoI of >= 10 x the pooled size): formed on the fly instead of once per RoI
@@ -260,12 +233,12 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
       if (!padrow && hb != cur) { want = hb; break; }           // needs another image: keep the RoI, go to the rendezvous
       // take the NEXT RoI now: its record is in flight while this one is pooled
       int rn;
-      { int t = 0; if (lane == 0) t = atomicAdd(&s_next, 1); rn = map_uni(t); }
+      { int t = 0; if (lane == 0) t = atomicAdd(&s_next, 1); rn = uni(t); }
       MapRec recn = rec;
       if (rn < r_end) fetch(rn, recn);
       TOut* orow = out + ((size_t)hr * p.channels + c0) * bins;
       if (padrow) {                            // padding row of a fixed-shape batch: defined output
-        for (int o = lane; o < nc * bins; o += 64) orow[o] = from_f32<TOut>(0.f);
+        for (int o = lane; o < nc * bins; o += 64) orow[o] = from_f32<TOut>(0.f);     // (not zero_outputs(): with it the PREP kernels lay out the branch around this loop differently)
         ri = rn; rec = recn;
         continue;
       }
@@ -383,7 +356,7 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
           __builtin_amdgcn_wave_barrier();
           const int n4 = (CG * bins) >> 2;
-          for (int i = lane; i < n4; i += 64) map_store4<TOut>(orow + 4 * i, reinterpret_cast<const float4*>(slab)[i]);
+          for (int i = lane; i < n4; i += 64) store4<TOut>(orow + 4 * i, reinterpret_cast<const float4*>(slab)[i]);
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
           __builtin_amdgcn_wave_barrier();
         } else if (on) {
@@ -421,7 +394,7 @@ __global__ __launch_bounds__(kMapThreads) void roi_align_fwd_map(RoiAlignParams 
         for (int u = 0; u < SU; u++) {
           const int e = min(base + u * kMapThreads, total - 1);
           const int c = e / n4, g = e - c * n4;
-          v[u] = MapLoad4<TIn>::ld(src + (int64_t)min(c, nc - 1) * L.stride_c + 4 * g);   // channel tail: duplicate, never stored
+          v[u] = load4(src + (int64_t)min(c, nc - 1) * L.stride_c + 4 * g);   // channel tail: duplicate, never stored
         }
 #pragma unroll
         for (int u = 0; u < SU; u++) {

@@ -35,25 +35,12 @@ constexpr int kNlBinRec = 96;                  // bytes per bin record: 16 tap o
 typedef __attribute__((address_space(3))) void nl_lds_void;
 typedef __attribute__((address_space(1))) const void nl_glb_void;
 
-__device__ __forceinline__ int nl_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // float32 maps only: a lane's 16 bytes of a pixel are 4 channels, a workgroup's 256-byte chunk is 64 (16-bit channels_last maps are
 // served by the direct-gather kernels, roi_align_nhwc16.hip and roi_align.hip)
 constexpr int kNlLaneCh = 4;
 constexpr int kNlCb = 16 * kNlLaneCh;
 __device__ __forceinline__ void nl_widen(const u32x4& r, float (&v)[kNlLaneCh]) {
   v[0] = __uint_as_float(r.x); v[1] = __uint_as_float(r.y); v[2] = __uint_as_float(r.z); v[3] = __uint_as_float(r.w);
-}
-
-template <typename TOut> __device__ __forceinline__ void nl_store4(TOut* d, float4 v);
-template <> __device__ __forceinline__ void nl_store4<float>(float* d, float4 v) { store_stream16(d, v); }     // streaming stores: dtc_common.h
-template <> __device__ __forceinline__ void nl_store4<__half>(__half* d, float4 v) {
-  const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-  store_stream8(d, *reinterpret_cast<const uint32_t*>(&a), *reinterpret_cast<const uint32_t*>(&b));
-}
-template <> __device__ __forceinline__ void nl_store4<bf16_t>(bf16_t* d, float4 v) {
-  store_stream8(d, (uint32_t)from_f32<bf16_t>(v.x).bits | ((uint32_t)from_f32<bf16_t>(v.y).bits << 16),
-                (uint32_t)from_f32<bf16_t>(v.z).bits | ((uint32_t)from_f32<bf16_t>(v.w).bits << 16));
 }
 
 
@@ -70,17 +57,14 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
   float* slab = reinterpret_cast<float*>(smem + 1024 + kNlMaxBins * kNlBinRec);
   unsigned char* img = smem + 1024 + kNlMaxBins * kNlBinRec + (size_t)CB * bins * 4;
   const uint32_t img32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)img;
-  const int tid = threadIdx.x, lane = tid & 63, wv = nl_uni(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
   const int nct = p.channels / CB;
   const int wi = xcd_work_item(blockIdx.x, gridDim.x, p.xcd_remap);
   const int ri = wi / nct;
   const int c0 = (wi - ri * nct) * CB;
   const RoiHead hd = load_roi_head(p, ri);
   TOut* out = reinterpret_cast<TOut*>(p.out) + ((size_t)hd.r * p.channels + c0) * bins;
-  if (hd.lvl < 0 || hd.lvl >= p.n_levels) {            // padding row of a fixed-shape batch: defined output
-    for (int o = tid; o < CB * bins; o += kNlThreads) out[o] = from_f32<TOut>(0.f);
-    return;
-  }
+  if (hd.lvl < 0 || hd.lvl >= p.n_levels) { zero_outputs<TOut, kNlThreads>(out, CB * bins, tid); return; }
   const dtc_feat_level L = p.lv[hd.lvl];
   const int H = L.height, W = L.width;
   // ---- axis samples (roi_align_cpu_loop.cpp:36-95), one thread per sample ------------------------------------------------------
@@ -204,7 +188,7 @@ __global__ __launch_bounds__(kNlThreads) void roi_align_fwd_nhwc_lds(RoiAlignPar
   // ---- slab [CB][bins] is one contiguous run of the [R,C,PH,PW] output: 16-byte stores ------------------------------------------------
   const int n4 = (CB * bins) >> 2;
   if (((CB * bins) & 3) == 0) {
-    for (int i = tid; i < n4; i += kNlThreads) nl_store4<TOut>(out + 4 * i, reinterpret_cast<const float4*>(slab)[i]);
+    for (int i = tid; i < n4; i += kNlThreads) store4<TOut>(out + 4 * i, reinterpret_cast<const float4*>(slab)[i]);
   } else {
     for (int i = tid; i < CB * bins; i += kNlThreads) out[i] = from_f32<TOut>(slab[i]);
   }
@@ -255,17 +239,13 @@ constexpr int kNpTabBytes = kNpSlots * 2 * kNpTabEntries * (int)(sizeof(NpTab) +
 constexpr int kNpHdrBytes = kNpTabBytes + kNpSlots * (int)sizeof(NpDesc) + kNpSlots * 32;             // + descriptors + NpGlb (24 -> 32 B)
 constexpr int kNpScrPitch = 5;                              // dwords per channel of a wave's transposition scratch (4 bins + 1: conflict-free)
 
-__device__ __forceinline__ float np_unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 __device__ __forceinline__ int np_rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
 // 16 bytes per lane, lane-linear into LDS at lds_dst (wave-uniform); source = wave-uniform 64-bit base (SGPR pair) + 32-bit lane
 // offset: no 64-bit vector arithmetic per instruction.  Not counted by the compiler.
 __device__ __forceinline__ void np_glds16s(uint32_t voff, const void* sbase_, uint32_t lds_dst_) {
-  // (readfirstlane: free when the value already lives in SGPRs, and makes the operands provably uniform when it is loop-carried)
-  const uint64_t sb = reinterpret_cast<uint64_t>(sbase_);
-  const void* sbase = reinterpret_cast<const void*>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sb >> 32)) << 32) |
-                                                    (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sb));
-  const uint32_t lds_dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_dst_);
+  const void* sbase = uni(sbase_);      // (loop-carried in issue_dma: wave_ops.h)
+  const uint32_t lds_dst = (uint32_t)uni((int)lds_dst_);
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(sbase) : "memory");
@@ -288,7 +268,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
   unsigned char* img0 = smem + kNpHdrBytes + (size_t)kNpPoolWaves * CB * kNpScrPitch * 4;
   const uint32_t img32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)img0;
   const uint32_t img_bytes = (uint32_t)img_pixels * kNlChunk;
-  const int tid = threadIdx.x, lane = tid & 63, wv = nl_uni(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
   const int q = lane & 15;
   const int nct = p.channels / CB;
   // ---- this workgroup's items: XCD x (= block % 8) owns a contiguous slice of the (RoI, channel block) items in visiting order; its
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     auto load_raw = [&](int ri) {
       if (!DESC) return load_roi_raw(p, ri);
       typedef __attribute__((address_space(4))) const float cfl;
-      const cfl* d = reinterpret_cast<cfl*>(reinterpret_cast<uintptr_t>(p.roi_desc)) + (size_t)nl_uni(ri) * 8;
+      const cfl* d = reinterpret_cast<cfl*>(reinterpret_cast<uintptr_t>(p.roi_desc)) + (size_t)uni(ri) * 8;
       RoiRaw w;
       w.d0 = make_float4(d[0], d[1], d[2], d[3]); w.d1 = make_float4(d[4], d[5], d[6], d[7]);
       return w;
@@ -328,22 +308,22 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
       const int c0 = (wi - ri * nct) * CB;
       const RoiHead hd = roi_head_from_raw(p, raw_pre);
       if (wi + step < item_end) raw_pre = load_raw((wi + step) / nct);
-      const int lvl = nl_uni(hd.lvl);
+      const int lvl = uni(hd.lvl);
       i_par = next_par; next_par = next_par == kNpSlots - 1 ? 0 : next_par + 1;
-      i_out = reinterpret_cast<float*>(p.out) + ((size_t)nl_uni(hd.r) * p.channels + c0) * bins;
+      i_out = reinterpret_cast<float*>(p.out) + ((size_t)uni(hd.r) * p.channels + c0) * bins;
       if (lvl < 0 || lvl >= p.n_levels) { i_mode = 2; i_x0 = i_y0 = 0; i_w = 1; i_fbase = nullptr; i_sh = i_sw = 0; return; }
       const dtc_feat_level L = p.lv[lvl];
-      const float sh = np_unif(hd.sh), sw = np_unif(hd.sw), bh = np_unif(hd.bin_h), bw = np_unif(hd.bin_w);
+      const float sh = uni(hd.sh), sw = uni(hd.sw), bh = uni(hd.bin_h), bw = uni(hd.bin_w);
       // lanes 0 .. 2 PH - 1: y samples; lanes 32 .. 32 + 2 PW - 1: x samples (roi_align_cpu_loop.cpp:36-95)
       const bool isx = lane >= 32;
       const int si = isx ? lane - 32 : lane;
-      const int LH = nl_uni(L.height), LW = nl_uni(L.width);      // (opaque: a select of the two FIELDS becomes a vector load of a selected address)
+      const int LH = uni(L.height), LW = uni(L.width);      // (opaque: a select of the two FIELDS becomes a vector load of a selected address)
       const AxisEntry e = make_axis(isx ? sw : sh, isx ? bw : bh, si >> 1, si & 1, 2, isx ? LW : LH);
       ylo_r = e.lo; yhi_r = e.hi;
       i_x0 = np_rl(e.lo, 32); i_y0 = np_rl(e.lo, 0);      // sample positions are non-decreasing: first .lo / last .hi
-      const int x1 = np_rl(e.hi, nl_uni(32 + 2 * PW - 1));
+      const int x1 = np_rl(e.hi, uni(32 + 2 * PW - 1));
       i_w = x1 - i_x0 + 1;
-      i_fbase = reinterpret_cast<const float*>(L.data) + (int64_t)nl_uni(hd.b) * L.stride_n + c0;
+      i_fbase = reinterpret_cast<const float*>(L.data) + (int64_t)uni(hd.b) * L.stride_n + c0;
       i_sh = L.stride_h; i_sw = L.stride_w;
       // plain channels_last strides and 16-byte alignment: what the LDS-DMA staging needs
       const bool dma_ok = L.stride_c == 1 && ((L.stride_w * (int64_t)sizeof(float)) & 15) == 0 && ((L.stride_h * (int64_t)sizeof(float)) & 15) == 0 &&
@@ -369,10 +349,10 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
       if (i_mode == 2) {
         pb = PH;
       } else {
-        ys = np_rl(ylo_r, nl_uni(2 * pa));
+        ys = np_rl(ylo_r, uni(2 * pa));
         pb = pa;
         while (pb < PH) {
-          const int h2 = np_rl(yhi_r, nl_uni(2 * pb + 1)) - ys + 1;
+          const int h2 = np_rl(yhi_r, uni(2 * pb + 1)) - ys + 1;
           if (h2 * i_w > img_pixels) break;
           hs = h2; pb++;
         }
@@ -415,7 +395,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     int k = 0;
     while (true) {
       __syncthreads();                                        // T(k)
-      if (!(nl_uni(ud[k % kNpSlots].flags) & 1)) break;
+      if (!(uni(ud[k % kNpSlots].flags) & 1)) break;
       plan_next((k + 2) % kNpSlots);                         // unit k+2 (the slot of unit k-1, pooled before T(k))
       k++;
     }
@@ -434,12 +414,12 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
   auto read_desc = [&](int slot_i) {
     const NpDesc d = ud[slot_i];
     NpU u;
-    u.flags = nl_uni(d.flags);
-    const int rows = nl_uni(d.rows), wh = nl_uni(d.wh);
-    u.pa = rows & 255; u.pb = rows >> 8; u.strip_off = nl_uni(d.strip_off); u.w = wh & 0xffff; u.hs = wh >> 16;
-    u.shb = nl_uni(d.shb); u.swb = nl_uni(d.swb);
-    u.out_lo = (uint32_t)nl_uni((int)d.out_lo); u.out_hi = (uint32_t)nl_uni((int)d.out_hi);
-    u.wb_lo = (uint32_t)nl_uni((int)d.wb_lo); u.wb_hi = (uint32_t)nl_uni((int)d.wb_hi);
+    u.flags = uni(d.flags);
+    const int rows = uni(d.rows), wh = uni(d.wh);
+    u.pa = rows & 255; u.pb = rows >> 8; u.strip_off = uni(d.strip_off); u.w = wh & 0xffff; u.hs = wh >> 16;
+    u.shb = uni(d.shb); u.swb = uni(d.swb);
+    u.out_lo = (uint32_t)uni((int)d.out_lo); u.out_hi = (uint32_t)uni((int)d.out_hi);
+    u.wb_lo = (uint32_t)uni((int)d.wb_lo); u.wb_hi = (uint32_t)uni((int)d.wb_hi);
     return u;
   };
   // LDS-DMA of a unit's window [ys, ys + hs) x [x0, x0 + w) into image `buf`: a wave-instruction moves 4 pixels x 256 B, lane-linear;
@@ -457,7 +437,7 @@ __global__ __launch_bounds__(kNpThreads, 4) void roi_align_fwd_nhwc_pipe(RoiAlig
     int row = (int)(((float)p0 + 0.5f) * rw);                          // exact: p0 < 2^13
     int col = p0 - row * w;
     uint32_t off = (uint32_t)row * shb + (uint32_t)col * swb + (uint32_t)q * 16u;
-    const int drow = nl_uni((int)(((float)(4 * kNpPoolWaves) + 0.5f) * rw)), dcol = 4 * kNpPoolWaves - drow * w;      // 28 = drow * w + dcol
+    const int drow = uni((int)(((float)(4 * kNpPoolWaves) + 0.5f) * rw)), dcol = 4 * kNpPoolWaves - drow * w;      // 28 = drow * w + dcol
     const uint32_t dstep = (uint32_t)drow * shb + (uint32_t)dcol * swb, wrapfix = shb - (uint32_t)w * swb;
     int kk = pwv;
     for (; kk + kNpPoolWaves < nk; kk += kNpPoolWaves) {               // every group but possibly the window's last one is whole
@@ -605,10 +585,21 @@ static bool np_plan(NpPlan& pl) {
   const int room = pl.lds_b - kNpHdrBytes - kNpPoolWaves * kNlCb * kNpScrPitch * 4;
   pl.img_pixels = room < 0 ? 0 : ((room / 2 / kNlChunk) & ~3);       // two images; the DMA writes whole groups of 4 pixels
   if (pl.img_pixels > 8188) pl.img_pixels = 8188;                     // pixel indices stay exact in the float reciprocal
-  pl.wgs_per_cu = (160 * 1024) / pl.lds_b;
+  pl.wgs_per_cu = kCuLdsBytes / pl.lds_b;
   if (pl.wgs_per_cu > 4) pl.wgs_per_cu = 4;                           // 512 threads each, 2048 per CU
   if (pl.wgs_per_cu < 1) pl.wgs_per_cu = 1;
   return pl.img_pixels >= 16;
+}
+// The same for roi_align_fwd_nhwc_lds: [axis samples 1 KB][bin records][slab: kNlCb x bins float32] are fixed, the image takes the rest
+// of the 40 KB (four workgroups per CU).  No plan when the image would hold fewer than 16 + 3 pixels: the direct-gather kernel instead.
+struct NlPlan { int fixed, img_pixels; };
+static bool nl_plan(int bins, NlPlan& pl) {
+  const RoiAlignKnobs& cfg = roi_align_knobs();
+  pl.fixed = 1024 + kNlMaxBins * kNlBinRec + kNlCb * bins * 4;
+  const int room = ((cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 40) * 1024 - pl.fixed) / kNlChunk;
+  pl.img_pixels = room & ~3;                                          // the DMA writes whole groups of 4 pixels
+  if (pl.img_pixels > 8188) pl.img_pixels = 8188;                     // pixel indices stay exact in the float reciprocal
+  return room >= 16 + 3;
 }
 static bool np_takes(int bins, int in_dtype, int out_dtype) {
   const RoiAlignKnobs& cfg = roi_align_knobs();
@@ -624,7 +615,7 @@ bool roi_align_nhwc_lds_supported(const RoiAlignParams& p, int in_dtype, int out
   if (p.channels % kNlCb != 0) return false;
   if (np_takes(bins, in_dtype, out_dtype)) { NpPlan pl; if (!np_plan(pl)) return false; }
   // roi_align_fwd_nhwc_lds: <= 64 bins; the tables and the output slab must leave room for a window image (else: the direct-gather kernel)
-  else if (bins > kNlMaxBins || ((cfg.nhwc_lds_kb ? cfg.nhwc_lds_kb : 40) * 1024 - (1024 + kNlMaxBins * kNlBinRec + kNlCb * bins * 4)) / kNlChunk < 16 + 3) return false;
+  else { NlPlan pl; if (bins > kNlMaxBins || !nl_plan(bins, pl)) return false; }
   for (int l = 0; l < p.n_levels; l++)
     if (p.lv[l].stride_c != 1 || p.lv[l].height > 65535 || p.lv[l].width > 65535) return false;
   return io_pair_supported(in_dtype, out_dtype);
@@ -640,7 +631,7 @@ static int np_cus() {      // compute units of the device the launch goes to (MI
 }
 
 static int launch_np(const RoiAlignParams& p, hipStream_t stream) {
-  if (raise_lds_once<roi_align_fwd_nhwc_pipe<true>, roi_align_fwd_nhwc_pipe<false>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_nhwc_pipe<true>, roi_align_fwd_nhwc_pipe<false>>() != DTC_OK) return DTC_ELAUNCH;
   NpPlan pl;
   if (!np_plan(pl)) return DTC_EUNSUPPORTED;
   const long long n_items = (long long)p.n_rois * (p.channels / kNlCb);
@@ -660,15 +651,11 @@ static int launch_np(const RoiAlignParams& p, hipStream_t stream) {
 
 template <typename TOut>
 static int launch_nl_t(const RoiAlignParams& p, hipStream_t stream) {
-  if (raise_lds_once<roi_align_fwd_nhwc_lds<TOut>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
-  const int bins = p.pooled_h * p.pooled_w;
-  const int fixed = 1024 + kNlMaxBins * kNlBinRec + kNlCb * bins * 4;
-  const int lds_b = (roi_align_knobs().nhwc_lds_kb ? roi_align_knobs().nhwc_lds_kb : 40) * 1024;
-  int img_pixels = ((lds_b - fixed) / kNlChunk) & ~3;           // the DMA writes whole groups of 4 pixels
-  if (img_pixels < 16) return DTC_EUNSUPPORTED;
-  if (img_pixels > 8188) img_pixels = 8188;                      // pixel indices stay exact in the float reciprocal
+  if (raise_lds_once<roi_align_fwd_nhwc_lds<TOut>>() != DTC_OK) return DTC_ELAUNCH;
+  NlPlan pl;
+  if (!nl_plan(p.pooled_h * p.pooled_w, pl)) return DTC_EUNSUPPORTED;
   const int nct = p.channels / kNlCb;
-  hipLaunchKernelGGL((roi_align_fwd_nhwc_lds<TOut>), dim3((unsigned)p.n_rois * nct), dim3(kNlThreads), fixed + img_pixels * kNlChunk, stream, p, img_pixels);
+  hipLaunchKernelGGL((roi_align_fwd_nhwc_lds<TOut>), dim3((unsigned)p.n_rois * nct), dim3(kNlThreads), pl.fixed + pl.img_pixels * kNlChunk, stream, p, pl.img_pixels);
   DTC_CHECK_LAUNCH();
   return DTC_OK;
 }

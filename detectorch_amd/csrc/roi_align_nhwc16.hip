@@ -254,7 +254,7 @@ __global__ __launch_bounds__(kN16Threads) void roi_align_fwd_nhwc16(RoiAlignPara
   __syncthreads();
   bool any_far = false;
   for (int k = 0; k < ng; k++) any_far = any_far || rinfo[k].far != 0u;
-  any_far = __builtin_amdgcn_readfirstlane((int)any_far) != 0;
+  any_far = uni((int)any_far) != 0;
 
   // ---- B. bins of all RoIs of the group, dealt over the lanes: item = slot, slot + kStep, ... ---------------------------------
   constexpr int NQ8 = CB / CPL, kStep = kN16Threads / NQ8;      // lanes per bin; bins per round

@@ -64,14 +64,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void* base) {
   // raw buffer, no bounds clamp (num_records = 2^32 - 1); word 3 = DATA_FORMAT 32 (the gfx9 raw-buffer encoding)
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xffffffff, 0x00020000);
 }
-// Piece4<T>::ld: four pixels of one channel as float32.  16-bit maps: Piece4<T>::raw keeps the four 16-bit values as loaded (two
+// Piece4<T>::raw: four pixels of one channel as loaded.  16-bit maps: the four 16-bit values stay as they are (two
 // dwords) -- the LDS image of a 16-bit map stays 16-bit (half the commit and tap bytes) and the taps are widened where they are
 // multiplied (mul_pair16: the same float32 values).
 template <typename TIn> struct Piece4;
 template <> struct Piece4<float> {
   typedef float4 Raw;
-  static __device__ __forceinline__ Raw raw(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) { return ld(r, voff, soff); }
-  static __device__ __forceinline__ float4 ld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+  static __device__ __forceinline__ Raw raw(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   }
@@ -79,23 +78,11 @@ template <> struct Piece4<float> {
 template <> struct Piece4<__half> {
   typedef u32x2 Raw;
   static __device__ __forceinline__ Raw raw(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0); }
-  static __device__ __forceinline__ float4 ld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    const uint32_t x = v.x, y = v.y;
-    const __half2 a = *reinterpret_cast<const __half2*>(&x), b = *reinterpret_cast<const __half2*>(&y);
-    return make_float4(__low2float(a), __high2float(a), __low2float(b), __high2float(b));
-  }
 };
 template <> struct Piece4<bf16_t> {
   typedef u32x2 Raw;
   static __device__ __forceinline__ Raw raw(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) { return __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0); }
-  static __device__ __forceinline__ float4 ld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    return bf16x4_to_f32(make_uint2(v.x, v.y));
-  }
 };
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // element type / slot size of the LDS image: float32 maps -> float32, 16 bytes per (pixel, 4 channels); 16-bit maps -> the raw 16-bit
 // values, 8 bytes per slot (tap = ds_read_b64; simulated on the bench RoIs, tools/r04/lds_taps4.py b64: 5.2 LDS cycles per tap read
@@ -117,17 +104,6 @@ struct TileItem {
   float yl[2], yh[2], xl[2], xh[2];
   bool on;
 };
-
-template <typename TOut> __device__ __forceinline__ void store_quad(TOut* d, float4 v);
-template <> __device__ __forceinline__ void store_quad<float>(float* d, float4 v) { store_stream16(d, v); }
-template <> __device__ __forceinline__ void store_quad<__half>(__half* d, float4 v) {
-  const __half2 a = __floats2half2_rn(v.x, v.y), b = __floats2half2_rn(v.z, v.w);
-  store_stream8(d, *reinterpret_cast<const uint32_t*>(&a), *reinterpret_cast<const uint32_t*>(&b));
-}
-template <> __device__ __forceinline__ void store_quad<bf16_t>(bf16_t* d, float4 v) {
-  store_stream8(d, (uint32_t)from_f32<bf16_t>(v.x).bits | ((uint32_t)from_f32<bf16_t>(v.y).bits << 16),
-                (uint32_t)from_f32<bf16_t>(v.z).bits | ((uint32_t)from_f32<bf16_t>(v.w).bits << 16));
-}
 
 enum { kStageScalar = 0, kStageVec = 1, kStageVecUnaligned = 2 };
 
@@ -277,7 +253,7 @@ __device__ __forceinline__ void tile_passes(const RoiAlignParams& p, const dtc_f
         const int e = idx - __mul24(k, n4);
         const float4 val = reinterpret_cast<const float4*>(slab)[idx];
         const uint64_t ob = *reinterpret_cast<const uint64_t*>(&troi[g.first + k].x0);
-        store_quad<TOut>(out + (ob + (uint64_t)(uint32_t)(cs_off + 4 * e)), val);
+        store4<TOut>(out + (ob + (uint64_t)(uint32_t)(cs_off + 4 * e)), val);
       }
     } else {
       const int per = nch * bins, total = g.count * per;
@@ -499,7 +475,7 @@ __global__ __launch_bounds__(NT, (TileBounds<TIn, NT>::kWaves)) void roi_align_f
     if (kind == kGrpAbsent) continue;
     if (kind == kGrpZero) {    // padding row of a fixed-shape batch (fpn.hip emits level -1): defined output
       TOut* oz = reinterpret_cast<TOut*>(p.out) + ((size_t)uni(troi[first].r) * p.channels + c0) * bins;
-      for (int o = tid; o < nc * bins; o += NT) oz[o] = from_f32<TOut>(0.f);
+      zero_outputs<TOut, NT>(oz, nc * bins, tid);
       continue;
     }
     const int lvl = uni(troi[first].lvl), b = uni(troi[first].b);
@@ -599,7 +575,7 @@ static int launch_tile_nt(RoiAlignParams p, hipStream_t stream) {
   if (K < 1) return DTC_EUNSUPPORTED;
   // 16-bit maps: their LDS image is half the size
   const int lds_b = (sizeof(TIn) == 2 ? (cfg.tile_lds16_kb ? cfg.tile_lds16_kb : TileShape<NT>::kLds16KB) : TileShape<NT>::kLdsKB) * 1024;
-  if (raise_lds_once<roi_align_fwd_tile<TIn, TOut, NT, FUSED>>(160 * 1024) != DTC_OK) return DTC_ELAUNCH;
+  if (raise_lds_once<roi_align_fwd_tile<TIn, TOut, NT, FUSED>>() != DTC_OK) return DTC_ELAUNCH;
   const int nq_cap = kTileNqCap;
   if (kTileHdrBytes + K * bins * 16 * nq_cap + 20 * 1024 > lds_b) return DTC_EUNSUPPORTED;
   const int ngrp = ceil_div(p.n_rois, K);

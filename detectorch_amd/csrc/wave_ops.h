@@ -6,6 +6,18 @@
 
 namespace dtc {
 
+// "This value is the same in every lane: keep it in SGPRs."  v_readfirstlane is free when the value already lives in SGPRs; it makes
+// a value provably uniform where the compiler cannot see that it is (loop-carried, read from LDS, an atomic's result handed out by
+// lane 0), so that what is formed from it is scalar arithmetic and scalar operands; and it is opaque to the optimiser, which
+// otherwise turns a uniform offset inside an unrolled loop into one induction variable per address.  int and float are one
+// instruction, 64-bit integers and pointers two.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uni(float v) { return __int_as_float(uni(__float_as_int(v))); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) {
+  return ((uint64_t)(uint32_t)uni((int)(uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)uni((int)(uint32_t)v);
+}
+template <typename T> __device__ __forceinline__ T* uni(T* p) { return reinterpret_cast<T*>(uni(reinterpret_cast<uint64_t>(p))); }
+
 // Inclusive prefix sum of v over the lanes of a wavefront: six __shfl_up steps (int, uint32_t or long long).
 template <typename T> __device__ __forceinline__ T wave_incl_scan(T v, int lane) {
 #pragma unroll
