@@ -2,7 +2,8 @@
 
     python -m detectorch_amd.build [--force]
 
-build_train() does the same for the training-side natives (csrc/train/*.hip -> libdetectorch_train_hip.so).
+build_train() does the same for the training-side natives (csrc/train/*.hip -> libdetectorch_train_hip.so), build_loss() for
+the head losses and their gradients (csrc/loss/*.hip -> libdetectorch_loss_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -70,43 +71,63 @@ def build(force=False, verbose=False):
     return LIB
 
 
-# ---- the training-side natives: a second library (include/detectorch_train_hip.h), so that the inference library's ABI stays as it is.
-# sources() globs csrc/*.hip only; csrc/train/*.hip include the csrc/ headers by include path and are built with the same FLAGS.
+# ---- the side libraries, so that the inference library's ABI stays as it is: the training-side natives (include/detectorch_train_hip.h)
+# and the head losses with their gradients (include/detectorch_loss_hip.h).  sources() globs csrc/*.hip only; csrc/train/*.hip and
+# csrc/loss/*.hip include the csrc/ headers by include path and are built with the same FLAGS, one library per directory.
 TRAIN_CSRC = os.path.join(CSRC, "train")
 TRAIN_LIB = os.path.join(LIBDIR, "libdetectorch_train_hip.so")
+LOSS_CSRC = os.path.join(CSRC, "loss")
+LOSS_LIB = os.path.join(LIBDIR, "libdetectorch_loss_hip.so")
 
 
-def train_sources():
-    return sorted(glob.glob(os.path.join(TRAIN_CSRC, "*.hip")))
+def _side_sources(csrc):
+    return sorted(glob.glob(os.path.join(csrc, "*.hip")))
 
 
-def needs_build_train():
-    if not os.path.exists(TRAIN_LIB):
+def _needs_side_build(lib, csrc):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(TRAIN_LIB)
-    deps = (train_sources() + glob.glob(os.path.join(TRAIN_CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.h")) +
+    t = os.path.getmtime(lib)
+    deps = (_side_sources(csrc) + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(CSRC, "*.h")) +
             glob.glob(os.path.join(HERE, "..", "include", "*.h")))
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_train(force=False, verbose=False):
-    if not force and not needs_build_train():
-        return TRAIN_LIB
-    objdir = os.path.join(LIBDIR, "obj_train")
+def _build_side(lib, csrc, force, verbose):
+    if not force and not _needs_side_build(lib, csrc):
+        return lib
+    objdir = os.path.join(LIBDIR, "obj_" + os.path.basename(csrc))
     os.makedirs(objdir, exist_ok=True)
     cc = hipcc()
     objs = []
-    for src in train_sources():                  # a handful of files: one after the other
+    for src in _side_sources(csrc):              # a handful of files: one after the other
         objs.append(os.path.join(objdir, os.path.basename(src)[:-4] + ".o"))
         cmd = [cc] + FLAGS + ["-I" + CSRC, "-c", src, "-o", objs[-1]]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-    subprocess.check_call([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", TRAIN_LIB + ".tmp"] + objs)
-    os.replace(TRAIN_LIB + ".tmp", TRAIN_LIB)
-    return TRAIN_LIB
+    subprocess.check_call([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib + ".tmp"] + objs)
+    os.replace(lib + ".tmp", lib)
+    return lib
+
+
+def train_sources():
+    return _side_sources(TRAIN_CSRC)
+
+
+def needs_build_train():
+    return _needs_side_build(TRAIN_LIB, TRAIN_CSRC)
+
+
+def build_train(force=False, verbose=False):
+    return _build_side(TRAIN_LIB, TRAIN_CSRC, force, verbose)
+
+
+def build_loss(force=False, verbose=False):
+    return _build_side(LOSS_LIB, LOSS_CSRC, force, verbose)
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
+    print(build_loss(force="--force" in sys.argv, verbose=True))

@@ -39,7 +39,9 @@ def sample_rois_batched(proposals, proposal_counts, gt_boxes, gt_classes, gt_is_
         rand_keys = torch.randint(-2 ** 31, 2 ** 31, (B, G + P), dtype=torch.int32, device=proposals.device, generator=generator)
     raw = None
     if out is not None:
-        raw = dict(out, rois5=out["rois"], labels=out["labels_int32"], max_overlaps=None, max_classes=None)
+        raw = {k: out[k] for k in ("bbox_targets5", "bbox_targets", "bbox_inside_weights", "bbox_outside_weights", "keep_inds", "n_fg",
+                                   "n_rois")}                         # the entry's own names only: invoke refuses unknown ones
+        raw.update(rois5=out["rois"], labels=out["labels_int32"], max_overlaps=None, max_classes=None)
     raw = hip_train.fast_rcnn_targets(gt_boxes, gt_classes, gt_is_crowd, gt_counts, proposals, proposal_counts, im_scale, rand_keys,
                                       params, out=raw, expanded=expanded)
     return dict(rois=raw["rois5"], labels_int32=raw["labels"], bbox_targets=raw["bbox_targets"],
