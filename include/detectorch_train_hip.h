@@ -51,6 +51,9 @@ typedef struct dtc_train_params {
  *   rand_keys uint32 [B, G + P]: the sampling order, supplied by the caller.
  *   G <= 256, P <= 2048, R <= 4096 (DTC_EUNSUPPORTED beyond); G or P may be 0 (the pointers of an empty input may be NULL), G + P >= 1;
  *   gt_boxes and proposals 16-byte aligned.  Inputs must be FINITE boxes with x2 >= x1, y2 >= y1: this is not checked.
+ *   A count outside [0, stride] is CLAMPED on the device (a negative one reads as 0, one above the stride as the stride): no row
+ *   past the stride is read, and the result is that of the call with the clamped counts.  With a stride of 0 the counts pointer
+ *   of that input is not read either.
  * The CANDIDATES of image b are its gt rows (all gt_counts[b] of them, crowd included) followed by its proposal_counts[b] proposals:
  * candidate index c < n_cand = gt_counts[b] + proposal_counts[b]; rand_keys[b, c], keep_inds, max_overlaps and max_classes are
  * indexed by c.

@@ -11,11 +11,12 @@ import pytest
 import torch
 
 from conftest import golden
+import train_limit_cases as tl
 import train_targets_ref as tr
 
 pytestmark = pytest.mark.gpu
 
-EXPANDED = ("bbox_targets", "bbox_inside_weights", "bbox_outside_weights")
+EXPANDED = tl.EXPANDED
 
 
 @pytest.fixture(scope="module")
@@ -37,75 +38,10 @@ def want_of(case, params=None):
 
 def _batch(cases, G=None, P=None):
     """device inputs of a batch of cases, NaN / garbage past every count"""
-    cs = [tr.make_case(c) for c in cases]
-    B = len(cs)
-    G = max(len(c["gt_boxes"]) for c in cs) if G is None else G
-    P = max(len(c["proposals"]) for c in cs) if P is None else P
-    gt = np.full((B, G, 4), np.nan, np.float32)
-    cls = np.full((B, G), -12345, np.int32)
-    crowd = np.full((B, G), 1, np.int32)
-    prop = np.full((B, P, 4), np.nan, np.float32)
-    prop[:, :, 1] = 1e30
-    keys = np.full((B, G + P), 0xDEADBEEF, np.uint32)
-    for b, c in enumerate(cs):
-        ng, npr = len(c["gt_boxes"]), len(c["proposals"])
-        gt[b, :ng], cls[b, :ng], crowd[b, :ng], prop[b, :npr] = c["gt_boxes"], c["gt_classes"], c["is_crowd"], c["proposals"]
-        keys[b, :ng + npr] = c["rand_keys"]
-    d = lambda a: torch.from_numpy(a).cuda()
-    return dict(gt_boxes=d(gt), gt_classes=d(cls), gt_is_crowd=d(crowd),
-                gt_counts=d(np.array([len(c["gt_boxes"]) for c in cs], np.int32)), proposals=d(prop),
-                proposal_counts=d(np.array([len(c["proposals"]) for c in cs], np.int32)),
-                im_scale=d(np.array([c["im_scale"] for c in cs], np.float32)), rand_keys=d(keys.view(np.int32)))
+    return tl.batch([tr.make_case(c) for c in cases], G, P)
 
 
-def _run(x, params, out=None, expanded=True, assignment=True):
-    from detectorch_amd import hip_train
-    return hip_train.fast_rcnn_targets(x["gt_boxes"], x["gt_classes"], x["gt_is_crowd"], x["gt_counts"], x["proposals"],
-                                       x["proposal_counts"], x["im_scale"], x["rand_keys"], hip_train.train_params(**params),
-                                       out=out, expanded=expanded, assignment=assignment)
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in out.items()}
-
-
-def _check(o, b, want, params, bound, label):
-    """image b of the host copy `o` of the outputs against a restatement result"""
-    R, n, nf = params["rois_per_image"], want["n_rois"], want["n_fg"]
-    assert int(o["n_rois"][b]) == n and int(o["n_fg"][b]) == nf
-    nc = len(want["max_overlaps"])
-    if o["max_overlaps"] is not None:
-        assert tr.same_bits(o["max_overlaps"][b, :nc], want["max_overlaps"])
-        assert tr.same_bits(o["max_classes"][b, :nc], want["max_classes"])
-        assert not o["max_overlaps"][b, nc:].any() and not o["max_classes"][b, nc:].any()
-    assert tr.same_bits(o["keep_inds"][b, :n], want["keep_inds"]) and np.all(o["keep_inds"][b, n:] == -1)
-    assert tr.same_bits(o["labels"][b, :n], want["labels"]) and np.all(o["labels"][b, n:] == -1)
-    rois = want["rois"].copy()
-    rois[:, 0] = b
-    assert tr.same_bits(o["rois5"][b, :n], rois)
-    pad = np.zeros((R - n, 5), np.float32)
-    pad[:, 0] = b
-    assert tr.same_bits(o["rois5"][b, n:], pad)
-    t5 = o["bbox_targets5"][b]
-    assert tr.same_bits(t5[:n, :3], want["bbox_targets5"][:, :3]) and tr.same_bits(t5[n:], np.zeros((R - n, 5), np.float32))
-    u = tr.ulps_from(t5[:n, 3:], want["want64"][want["keep_inds"]])
-    worst = float(u.max(initial=0.0))
-    print("%s image %d: dw / dh at most %.3f ulp from w * log(float64(ratio)) (bound %.3f)" % (label, b, worst, bound))
-    assert worst <= bound
-    if o["bbox_targets"] is not None:
-        W = want["bbox_targets"].shape[1]
-        bt = o["bbox_targets"][b]
-        assert bt.shape == (R, W) and not bt[n:].any()
-        slot = np.zeros((n, W), bool)                                        # the expanded targets are the compact ones, in their slot
-        for r in np.where(want["bbox_targets5"][:, 0] > 0)[0]:
-            c = int(want["bbox_targets5"][r, 0])
-            slot[r, 4 * c:4 * c + 4] = True
-            assert tr.same_bits(bt[r, 4 * c:4 * c + 4], t5[r, 1:])
-        assert not bt[:n][~slot].any()
-        for k in ("bbox_inside_weights", "bbox_outside_weights"):
-            assert tr.same_bits(o[k][b, :n], want[k]) and not o[k][b, n:].any()
-    return worst
+_run, _host, _check = tl.run, tl.host, tl.check                              # shared with tests/test_hip_train_limits.py
 
 
 @pytest.mark.parametrize("case", sorted(tr.CASES))
