@@ -75,6 +75,22 @@ size_t dtc_fast_rcnn_loss_workspace_bytes(int n, int c);
  *     such a class); a row with label >= C still counts in n_valid.
  *   Inputs on valid rows must be finite: this is not checked.  Ignored rows may hold any bits, NaN included: their cls_score,
  *   bbox_pred and bbox_targets5 are never read.
+ *   ANY finite float32 is admitted, denormals included.  Logits: only differences from the row maximum are formed, so a row
+ *   may span the whole float32 range as long as max - min is itself a float32 (+-1e38 in one row is); a softmax that is exactly
+ *   one-hot gives an exact 0 in the label's column on a hit and exactly -upstream[0] / n_valid on a miss.  Box terms: pred - target,
+ *   its square and the quotient by beta are formed in double, where none of them can overflow or vanish for float32 operands
+ *   and any float32 beta > 0 (2^-149 and 3e38 included); the results are rounded to float32 once, so a loss beyond the float32
+ *   range comes out as inf and a gradient element below the float32 normal range as the device rounds it.
+ *   A target class is compared as the float it is: -0.0 is class 0 (no box term); a denormal, any other non-integer (0.999,
+ *   C - 0.5), +-inf, NaN and any value >= C (2^24) give no box term and are never converted to an index.
+ *   upstream: any two finite floats, 0 and negative ones included; they scale the gradients only (the losses of a call do not
+ *   depend on them), a factor 0 gives gradients that compare equal to 0 (the sign of such a zero is not specified; the zeros of
+ *   ignored rows and unselected columns are +0.0), and they are read on the device when the kernels run: a graph replay uses the
+ *   values that are in the buffer at that time.
+ *   Alignment: bbox_pred, grad_bbox_pred and the workspace 16 bytes, as said above; every other pointer (cls_score, labels,
+ *   bbox_targets5, upstream, losses, grad_cls_score) needs the 4 bytes of its element type only.  Nothing is written outside the
+ *   stated extents of the outputs and the workspace.  A call that returns DTC_EINVAL, DTC_EUNSUPPORTED or DTC_EWORKSPACE has
+ *   launched nothing and written nothing.
  * The box terms and every cross-row sum are accumulated in double in a fixed order and rounded once; there are no float atomics:
  * the same inputs give the same bits on every run, eagerly and under graph replay.
  * Limits: 2 <= C <= DTC_LOSS_MAX_CLASSES, 1 <= N <= DTC_LOSS_MAX_ROWS (DTC_EUNSUPPORTED beyond; N < 1 or C < 2: DTC_EINVAL).
@@ -100,6 +116,10 @@ size_t dtc_smooth_l1_workspace_bytes(int n, int w);
  *   loss float32 [1] and / or grad_pred float32 [N, W] (not both NULL); upstream float32 [1] on the device or NULL for 1;
  *   workspace: needed for the loss only (NULL with loss == NULL), dtc_smooth_l1_workspace_bytes(n, w) bytes, 8-byte aligned.
  * N >= 1, W >= 1 (DTC_EINVAL), N * W <= DTC_LOSS_MAX_ELEMS (DTC_EUNSUPPORTED beyond).  Inputs must be finite: not checked.
+ * Any finite float32 is admitted for the four inputs and any float32 beta > 0, as for dtc_fast_rcnn_loss: weights of either sign,
+ * 0 (an exact-zero gradient element) and of any magnitude; x, x^2 / beta and the products with the weights are formed in double.
+ * N * W need not be a multiple of 4 and may be below 4; the row structure only sets the divisor.  loss and grad_pred are the same
+ * bits whether they are asked for together or one at a time.  Nothing is written past grad_pred[N * W - 1].
  * One kernel node for the gradient alone, two with the loss (the pass, then the sum of the workgroups' partial results). */
 int dtc_smooth_l1(const float* pred, const float* targets, const float* alpha_in, const float* alpha_out, int n, int w, float beta,
                   const float* upstream, void* workspace, size_t workspace_bytes, float* loss, float* grad_pred,
