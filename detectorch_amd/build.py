@@ -4,7 +4,8 @@
 
 build_train() does the same for the training-side natives (csrc/train/*.hip -> libdetectorch_train_hip.so), build_loss() for
 the head losses and their gradients (csrc/loss/*.hip -> libdetectorch_loss_hip.so), build_grad() for the gradients of the region
-operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so).
+operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so), build_optim() for the optimizer tail of the training step
+(csrc/optim/*.hip -> libdetectorch_optim_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -73,15 +74,18 @@ def build(force=False, verbose=False):
 
 
 # ---- the side libraries, so that the inference library's ABI stays as it is: the training-side natives (include/detectorch_train_hip.h),
-# the head losses with their gradients (include/detectorch_loss_hip.h) and the gradients of the region operators
-# (include/detectorch_grad_hip.h).  sources() globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip and csrc/grad/*.hip include the
-# csrc/ headers by include path and are built with the same FLAGS, one library per directory.
+# the head losses with their gradients (include/detectorch_loss_hip.h), the gradients of the region operators
+# (include/detectorch_grad_hip.h) and the clipped SGD step (include/detectorch_optim_hip.h).  sources() globs csrc/*.hip only;
+# csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip and csrc/optim/*.hip include the csrc/ headers by include path and are built
+# with the same FLAGS, one library per directory.
 TRAIN_CSRC = os.path.join(CSRC, "train")
 TRAIN_LIB = os.path.join(LIBDIR, "libdetectorch_train_hip.so")
 LOSS_CSRC = os.path.join(CSRC, "loss")
 LOSS_LIB = os.path.join(LIBDIR, "libdetectorch_loss_hip.so")
 GRAD_CSRC = os.path.join(CSRC, "grad")
 GRAD_LIB = os.path.join(LIBDIR, "libdetectorch_grad_hip.so")
+OPTIM_CSRC = os.path.join(CSRC, "optim")
+OPTIM_LIB = os.path.join(LIBDIR, "libdetectorch_optim_hip.so")
 
 
 def _side_sources(csrc):
@@ -92,7 +96,7 @@ def _needs_side_build(lib, csrc):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = (_side_sources(csrc) + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(CSRC, "*.h")) +
+    deps = (_side_sources(csrc) + glob.glob(os.path.join(CSRC, "*", "*.h")) + glob.glob(os.path.join(CSRC, "*.h")) +
             glob.glob(os.path.join(HERE, "..", "include", "*.h")))
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -135,8 +139,13 @@ def build_grad(force=False, verbose=False):
     return _build_side(GRAD_LIB, GRAD_CSRC, force, verbose)
 
 
+def build_optim(force=False, verbose=False):
+    return _build_side(OPTIM_LIB, OPTIM_CSRC, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
     print(build_loss(force="--force" in sys.argv, verbose=True))
     print(build_grad(force="--force" in sys.argv, verbose=True))
+    print(build_optim(force="--force" in sys.argv, verbose=True))

@@ -17,7 +17,8 @@ Differences from the reference:
     region path -> heads -> detections -> mask branch for B images with no host round trip, on the same fused batched
     kernels bench.py measures (detectorch_amd.pipeline.FpnRegionPath); `forward` stays the reference's batch-1 call;
   * `head_dtype=torch.bfloat16`: RoIAlign writes the pooled features in bf16 and fc6/fc7 run as bf16 MFMA GEMMs;
-  * inference only (the reference's README.md:3 scope).
+  * the constructor and forward() are inference only (the reference's README.md:3 scope); `forward_train(images, rois5)` is the
+    grad-enabled forward of the one configuration the reference trains (train_fast.py), see detectorch_amd/train.py.
 """
 import contextlib
 import pickle
@@ -31,7 +32,7 @@ import torch.nn.functional as F
 from .. import hip
 from .collect_and_distribute_fpn_rpn_proposals import CollectAndDistributeFpnRpnProposals
 from .generate_proposals import GenerateProposals
-from .roi_align import RoIAlignFunction, preprocess_rois
+from .roi_align import RoIAlign, RoIAlignFunction, preprocess_rois
 
 
 # ---- ResNet body (torchvision-compatible names) ------------------------------------------------------------------------
@@ -416,6 +417,26 @@ class detector(nn.Module):
             cls_score = F.softmax(cls_score, dim=1)
         bbox_pred = self.bbox_head(roi_features)
         return cls_score, bbox_pred, rois, img_features
+
+    def forward_train(self, images, rois5):
+        """The grad-enabled forward of the configuration the reference trains (train_fast.py:78-83, :134): the defaults of
+        detector(), R-50/101-C4 Fast R-CNN on given proposals.  images [B,3,H,W]; rois5 float32 [N,5] = (batch index, x1, y1, x2, y2)
+        in blob coordinates: the `rois` blob of sample_rois_batched viewed as rows, padding rows included (the losses ignore them).
+        conv_body -> RoIAlign with its native backward -> res5 head -> (cls_score [N,C] logits: no softmax, bbox_pred [N,4C]).
+        Anything else raises NotImplementedError; forward / forward_batched stay the inference entries."""
+        if (self.use_fpn_body or self.use_rpn_head or self.use_mask_head or self.use_two_layer_mlp_head or self.channels_last
+                or getattr(self, "_optimized", False) or self.head_dtype not in (None, torch.float32)
+                or self.backbone_dtype not in (None, torch.float32)):
+            raise NotImplementedError("forward_train covers Fast R-CNN R-50/101-C4 on given proposals in float32 (the defaults of "
+                                      "detector())")
+        hip._require_cuda(images, rois5)
+        if images.dim() != 4 or rois5.dim() != 2 or rois5.shape[1] != 5:
+            raise ValueError("forward_train takes images [B,3,H,W] and rois5 [N,5] (batch index first)")
+        img_features = self.conv_body(images)
+        roi_features = RoIAlign(self.roi_height, self.roi_width, self.roi_spatial_scale, self.roi_sampling_ratio)(
+            img_features, rois5.detach().to(torch.float32).contiguous())
+        x = self._head(roi_features)
+        return self.classif_head(x), self.bbox_head(x)
 
     def _head(self, roi_features):
         """conv_head (fc6/fc7 or res5) on pooled features; head_dtype runs it as a low-precision MFMA GEMM, fp32 out."""
