@@ -438,6 +438,32 @@ class detector(nn.Module):
         x = self._head(roi_features)
         return self.classif_head(x), self.bbox_head(x)
 
+    def forward_train_rpn(self, images):
+        """The grad-enabled RPN forward of the use_rpn_head=True models, C4 and FPN, in float32 and not optimised: images [B,3,H,W]
+        -> (cls_logits_list, bbox_pred_list, img_features): one [B,A,H,W] map of PRE-sigmoid logits and one [B,4A,H,W] map of box
+        deltas per RPN level (FPN: the extra pooled level included, detector.py:250), in the level order of rpn_train_levels();
+        img_features as conv_body returns them (a tensor for C4, the list of FPN levels).  Anything else raises NotImplementedError."""
+        if (not self.use_rpn_head or self.channels_last or getattr(self, "_optimized", False)
+                or getattr(self, "_opt_dtype", None) is not None or self.head_dtype not in (None, torch.float32)
+                or self.backbone_dtype not in (None, torch.float32)):
+            raise NotImplementedError("forward_train_rpn covers the use_rpn_head=True models (C4 and FPN) in float32, NCHW, not optimised")
+        hip._require_cuda(images)
+        if images.dim() != 4:
+            raise ValueError("forward_train_rpn takes images [B,3,H,W]")
+        img_features = self.conv_body(images)
+        feats = list(img_features) if self.use_fpn_body else [img_features]
+        if self.use_fpn_body and self.fpn_extra_lvl:
+            feats = feats + [F.max_pool2d(feats[-1], 1, stride=2)]
+        outs = [self.rpn(f, logits=True) for f in feats]
+        return [c for c, _ in outs], [b for _, b in outs], img_features
+
+    def rpn_train_levels(self, cls_logits_list):
+        """The level records (anchor numbering, base anchors, strides) of rpn_targets_batched for the maps forward_train_rpn returned."""
+        from ..utils.rpn_targets import rpn_levels
+        gens = list(self.proposal_generator) if self.use_fpn_body else [self.proposal_generator]
+        scales = self.rpn_scales if self.use_fpn_body else [gens[0]._spatial_scale]
+        return rpn_levels([tuple(c.shape[1:]) for c in cls_logits_list], [g._anchors for g in gens], [1. / s for s in scales])
+
     def _head(self, roi_features):
         """conv_head (fc6/fc7 or res5) on pooled features; head_dtype runs it as a low-precision MFMA GEMM, fp32 out."""
         if getattr(self, "_opt_dtype", None) is not None:          # weights already live in the 16-bit type

@@ -7,6 +7,7 @@ elementwise and reduction kernels; plus the fused forms that read the compact, p
     cross_entropy(cls_score, labels)                            mean softmax cross-entropy over the rows with label >= 0
     fast_rcnn_losses(cls_score, bbox_pred, blobs, beta=1.0)     -> (loss_cls, loss_bbox, accuracy), differentiable
     fast_rcnn_losses_fused(cls_score, bbox_pred, blobs, ...)    losses AND both gradients from one call (graph capture)
+    rpn_losses(cls_logits_list, bbox_pred_list, blobs, beta=1/9) -> (loss_rpn_cls, loss_rpn_bbox) over the RPN maps, differentiable
 
 Differences a caller can observe (include/detectorch_loss_hip.h has the full contract):
   * GPU only: CPU tensors raise;
@@ -19,7 +20,7 @@ Differences a caller can observe (include/detectorch_loss_hip.h has the full con
 import torch
 from torch.autograd import Function
 
-from .. import hip_loss
+from .. import hip_loss, hip_rpn
 from ..hip import _require_cuda
 
 
@@ -111,6 +112,39 @@ def fast_rcnn_losses_fused(cls_score, bbox_pred, blobs, out=None, beta=1.0, upst
     cls_score, bbox_pred, labels, t5 = _head_args(cls_score, bbox_pred, blobs)
     return hip_loss.fast_rcnn_loss(_as_input(cls_score.detach()), labels, _as_input(bbox_pred.detach()), t5, beta=beta,
                                    upstream=upstream, out=out)
+
+
+class RpnLossFunction(Function):
+    """(loss_rpn_cls, loss_rpn_bbox) of dtc_rpn_loss over the per-level maps (n cls_logits maps, then n bbox_pred maps, as
+    RoIAlignFPNFunction takes its maps): forward is one loss-only call, backward one call that writes the dense gradient maps with the
+    two incoming gradients as its device-side `upstream`."""
+    @staticmethod
+    def forward(ctx, labels, fg_index, fg_targets, n_fg, n_bg, beta, *maps):
+        n = len(maps) // 2
+        ctx.save_for_backward(labels, fg_index, fg_targets, n_fg, n_bg, *maps)
+        ctx.beta = float(beta)
+        levels, _, _ = hip_rpn.map_levels(maps[:n], maps[n:])
+        losses = hip_rpn.rpn_loss(levels, labels, fg_index, fg_targets, n_fg, n_bg, beta=ctx.beta)["losses"]
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, grad_cls, grad_bbox):
+        labels, fg_index, fg_targets, n_fg, n_bg, *maps = ctx.saved_tensors
+        n = len(maps) // 2
+        upstream = torch.stack((grad_cls.detach().reshape(()), grad_bbox.detach().reshape(()))).to(torch.float32).contiguous()
+        grads = [torch.empty_like(m) for m in maps]
+        levels, _, _ = hip_rpn.map_levels(maps[:n], maps[n:], grads[:n], grads[n:])
+        hip_rpn.rpn_loss(levels, labels, fg_index, fg_targets, n_fg, n_bg, beta=ctx.beta, upstream=upstream)
+        return (None,) * 6 + tuple(grads)
+
+
+def rpn_losses(cls_logits_list, bbox_pred_list, blobs, beta=1.0 / 9.0):
+    """The two RPN losses on the blobs of rpn_targets_batched (expanded=False is enough): cls_logits_list [B,A,H,W] and
+    bbox_pred_list [B,4A,H,W] per level, in the level order of the targets -> (loss_rpn_cls, loss_rpn_bbox), 0-dim device tensors,
+    differentiable in every map: sigmoid cross-entropy over the sampled anchors / their number, and smooth-L1 (beta 1/9) over the
+    sampled foreground anchors / the sample size per image, averaged over the images."""
+    maps = [_as_input(t) for t in list(cls_logits_list) + list(bbox_pred_list)]
+    return RpnLossFunction.apply(blobs["labels"], blobs["fg_index"], blobs["fg_targets"], blobs["n_fg"], blobs["n_bg"], beta, *maps)
 
 
 def cross_entropy(cls_score, labels):

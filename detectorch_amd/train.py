@@ -1,8 +1,16 @@
 """One training step of Fast R-CNN R-50/101-C4 on given proposals, the loop body of the reference's train_fast.py:125-166 on the
 native pieces: the minibatch of sample_rois_batched, detector.forward_train (RoIAlign with its native backward), the fused head
-losses (model.loss.fast_rcnn_losses) and ClippedSGD (gradient clipping + momentum SGD in one call).  RPN and mask training and the
-dataset are not here."""
+losses (model.loss.fast_rcnn_losses) and ClippedSGD (gradient clipping + momentum SGD in one call); and the two steps that train the
+RPN models the project serves: rpn_train_step (RPN only -- stage 1 of alternating training -- C4 and FPN) and faster_rcnn_train_step
+(the joint approximate Faster R-CNN step on C4), on the anchor minibatch of rpn_targets_batched and the fused RPN losses
+(model.loss.rpn_losses).  The joint step on FPN, mask training and the dataset are not here."""
+import torch
+
+from . import hip
 from .model import loss as _loss
+from .model.roi_align import RoIAlign
+from .utils.fast_rcnn_sample_rois import sample_rois_batched
+from .utils.rpn_targets import rpn_targets_batched
 from .utils.solver import adjust_learning_rate, get_lr_at_iter
 
 
@@ -33,3 +41,77 @@ def fast_rcnn_train_step(model, optimizer, images, blobs, it=None):
     (loss_cls + loss_bbox).backward()
     optimizer.step()
     return loss_cls.detach(), loss_bbox.detach(), acc
+
+
+def _set_lr(optimizer, it):
+    if it is not None:
+        lr = get_lr_at_iter(it)
+        if getattr(optimizer, "capturable", False):
+            optimizer.set_lr_(lr)
+        else:
+            adjust_learning_rate(optimizer, lr)
+
+
+def _rpn_forward_losses(model, images, gt, rpn_knobs):
+    """forward_train_rpn, the anchor minibatch against gt, the two RPN losses.  gt: dict of device tensors -- gt_boxes f32 [B,G,4]
+    (original image coordinates), gt_is_crowd i32 [B,G], gt_counts i32 [B], im_scale f32 [B], im_hw f32 [B,2] (the scaled image's own
+    size inside the padded blob); optional rpn_rand_keys [B,N]."""
+    cls_logits, bbox_pred, feats = model.forward_train_rpn(images)
+    levels = model.rpn_train_levels(cls_logits)
+    blobs = rpn_targets_batched(levels, gt["gt_boxes"], gt["gt_is_crowd"], gt["gt_counts"], gt["im_scale"], gt["im_hw"],
+                                rand_keys=gt.get("rpn_rand_keys"), **rpn_knobs)
+    loss_rpn_cls, loss_rpn_bbox = _loss.rpn_losses(cls_logits, bbox_pred, blobs)
+    return cls_logits, bbox_pred, feats, blobs, loss_rpn_cls, loss_rpn_bbox
+
+
+def rpn_train_step(model, optimizer, images, gt, it=None, **rpn_knobs):
+    """One RPN-only step (stage 1 of alternating training) of a use_rpn_head=True model, C4 or FPN: the learning rate of iteration
+    `it` from the solver, forward_train_rpn, rpn_targets_batched, rpn_losses, zero_grad, backward of loss_rpn_cls + loss_rpn_bbox,
+    optimizer.step() (ClippedSGD).  gt: see _rpn_forward_losses; **rpn_knobs: the keywords of rpn_targets_batched
+    (batch_size_per_im, ...).  -> (loss_rpn_cls, loss_rpn_bbox) as 0-dim device tensors; nothing syncs with the host."""
+    _set_lr(optimizer, it)
+    _, _, _, _, loss_rpn_cls, loss_rpn_bbox = _rpn_forward_losses(model, images, gt, rpn_knobs)
+    optimizer.zero_grad()
+    (loss_rpn_cls + loss_rpn_bbox).backward()
+    optimizer.step()
+    return loss_rpn_cls.detach(), loss_rpn_bbox.detach()
+
+
+def faster_rcnn_train_step(model, optimizer, images, gt, it=None, rpn_knobs=None, post_nms_top_n=2000, pre_nms_top_n=12000,
+                           **head_knobs):
+    """The joint approximate Faster R-CNN step on the C4 model (use_rpn_head=True, no FPN): RPN forward and losses; under no_grad,
+    the proposals of hip.generate_proposals with the training top-n (post-NMS <= 2048, the minibatch kernel's limit);
+    sample_rois_batched on those proposals and the gt, BOTH in blob coordinates with im_scale 1, so that `rois` needs no rescaling;
+    RoIAlign on the shared features, the res5 head and the two heads; fast_rcnn_losses; ONE backward of the four losses (the
+    proposals carry no gradient: "approximate"), optimizer.step().  gt: see _rpn_forward_losses, plus gt_classes i32 [B,G] and
+    optional rand_keys [B,G+P]; **head_knobs: the keywords of sample_rois_batched.
+    -> (loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, accuracy, blobs); nothing syncs with the host."""
+    if model.use_fpn_body:
+        raise NotImplementedError("the joint step covers the C4 model: on FPN the sampled RoIs would have to be distributed over the "
+                                  "levels for training")
+    if post_nms_top_n < 1 or post_nms_top_n > 2048:
+        raise ValueError("post_nms_top_n must be in 1 .. 2048 (the proposal rows of sample_rois_batched)")
+    _set_lr(optimizer, it)
+    cls_logits, bbox_pred, feats, _, loss_rpn_cls, loss_rpn_bbox = _rpn_forward_losses(model, images, gt, rpn_knobs or {})
+    B, h, w = images.shape[0], images.shape[2], images.shape[3]
+    with torch.no_grad():
+        gen = model.proposal_generator
+        boxes, _, counts, _, _, _ = hip.generate_proposals(
+            [cls_logits[0].detach()], [bbox_pred[0].detach()], [gen._anchors], [1. / gen._spatial_scale], h, w, [pre_nms_top_n],
+            post_nms_top_n, gen.rpn_nms_thresh, scores_are_logits=True, im_hw=gt["im_hw"])
+        proposals = boxes[:, 0].contiguous()                                  # [B, P, 4], blob coordinates
+        scale = gt["im_scale"].reshape(B, 1, 1)
+        gt_blob = (gt["gt_boxes"] * scale).contiguous()                       # one float32 multiply, as the RPN minibatch scales them
+        blobs = sample_rois_batched(proposals, counts[:, 0].contiguous(), gt_blob, gt["gt_classes"], gt["gt_is_crowd"],
+                                    gt["gt_counts"], torch.ones_like(gt["im_scale"]), rand_keys=gt.get("rand_keys"), expanded=False,
+                                    num_classes=model.N_classes, **head_knobs)
+        blobs["proposals"], blobs["proposal_counts"] = proposals, counts[:, 0]
+    rois = blobs["rois"]
+    roi_features = RoIAlign(model.roi_height, model.roi_width, model.roi_spatial_scale, model.roi_sampling_ratio)(
+        feats, rois.reshape(-1, rois.shape[-1]))
+    x = model._head(roi_features)
+    loss_cls, loss_bbox, acc = _loss.fast_rcnn_losses(model.classif_head(x), model.bbox_head(x), blobs)
+    optimizer.zero_grad()
+    (loss_rpn_cls + loss_rpn_bbox + loss_cls + loss_bbox).backward()
+    optimizer.step()
+    return loss_rpn_cls.detach(), loss_rpn_bbox.detach(), loss_cls.detach(), loss_bbox.detach(), acc, blobs
