@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from .. import hip
 from .collect_and_distribute_fpn_rpn_proposals import CollectAndDistributeFpnRpnProposals
 from .generate_proposals import GenerateProposals
-from .roi_align import RoIAlign, RoIAlignFunction, preprocess_rois
+from .roi_align import RoIAlign, RoIAlignFunction, preprocess_rois, roi_align_fpn
 
 
 # ---- ResNet body (torchvision-compatible names) ------------------------------------------------------------------------
@@ -456,6 +456,35 @@ class detector(nn.Module):
             feats = feats + [F.max_pool2d(feats[-1], 1, stride=2)]
         outs = [self.rpn(f, logits=True) for f in feats]
         return [c for c, _ in outs], [b for _, b in outs], img_features
+
+    def forward_train_mask(self, img_features, mask_rois5, roi_levels=None):
+        """The grad-enabled mask branch of the use_mask_head=True models in float32, NCHW, not optimised (detector.py:99-112 without the
+        sigmoid): img_features as conv_body / forward_train_rpn returns them; mask_rois5 float32 [N,5] = (batch index, x1, y1, x2, y2) in
+        blob coordinates: the mask_rois blob of mask_targets_batched viewed as rows, padding rows included (the loss ignores them).
+        C4 'upshare': RoIAlign 14 x 14 on res4 with its native backward -> the shared res5 -> transposed conv -> [N,81,14,14] logits.
+        FPN '1up4convs': roi_align_fpn with roi_levels int32 [N] (the mask_roi_levels blob) -> four convs -> transposed conv ->
+        [N,81,28,28] logits.  Anything else raises NotImplementedError."""
+        if (not self.use_mask_head or self.channels_last or getattr(self, "_optimized", False)
+                or getattr(self, "_opt_dtype", None) is not None or self.head_dtype not in (None, torch.float32)
+                or self.backbone_dtype not in (None, torch.float32)):
+            raise NotImplementedError("forward_train_mask covers the use_mask_head=True models in float32, NCHW, not optimised")
+        mh = self.mask_head
+        rois = mask_rois5.detach().to(torch.float32).reshape(-1, 5).contiguous()
+        if not self.use_fpn_body and self.mask_head_type == 'upshare':
+            hip._require_cuda(img_features, rois)
+            x = RoIAlign(mh.roi_height, mh.roi_width, mh.roi_spatial_scale, mh.roi_sampling_ratio)(img_features, rois)
+        elif self.use_fpn_body and self.mask_head_type == '1up4convs':
+            if roi_levels is None:
+                raise ValueError("forward_train_mask on FPN takes roi_levels (the mask_roi_levels blob)")
+            feats = list(img_features)[:len(mh.roi_spatial_scale)]
+            hip._require_cuda(rois, roi_levels, *feats)
+            x = roi_align_fpn(feats, mh.roi_spatial_scale, rois, roi_levels.detach().to(torch.int32).reshape(-1).contiguous(),
+                              mh.roi_height, mh.roi_width, mh.roi_sampling_ratio)
+        else:
+            raise NotImplementedError("forward_train_mask covers C4 with the 'upshare' head and FPN with the '1up4convs' head")
+        x = mh.conv_head(x)
+        x = F.relu(mh.transposed_conv(x))
+        return mh.classif_logits(x)
 
     def rpn_train_levels(self, cls_logits_list):
         """The level records (anchor numbering, base anchors, strides) of rpn_targets_batched for the maps forward_train_rpn returned."""

@@ -8,6 +8,7 @@ elementwise and reduction kernels; plus the fused forms that read the compact, p
     fast_rcnn_losses(cls_score, bbox_pred, blobs, beta=1.0)     -> (loss_cls, loss_bbox, accuracy), differentiable
     fast_rcnn_losses_fused(cls_score, bbox_pred, blobs, ...)    losses AND both gradients from one call (graph capture)
     rpn_losses(cls_logits_list, bbox_pred_list, blobs, beta=1/9) -> (loss_rpn_cls, loss_rpn_bbox) over the RPN maps, differentiable
+    mask_rcnn_loss(mask_logits, blobs)                          -> loss_mask over the blobs of mask_targets_batched, differentiable
 
 Differences a caller can observe (include/detectorch_loss_hip.h has the full contract):
   * GPU only: CPU tensors raise;
@@ -20,7 +21,7 @@ Differences a caller can observe (include/detectorch_loss_hip.h has the full con
 import torch
 from torch.autograd import Function
 
-from .. import hip_loss, hip_rpn
+from .. import hip_loss, hip_mask, hip_rpn
 from ..hip import _require_cuda
 
 
@@ -145,6 +146,31 @@ def rpn_losses(cls_logits_list, bbox_pred_list, blobs, beta=1.0 / 9.0):
     sampled foreground anchors / the sample size per image, averaged over the images."""
     maps = [_as_input(t) for t in list(cls_logits_list) + list(bbox_pred_list)]
     return RpnLossFunction.apply(blobs["labels"], blobs["fg_index"], blobs["fg_targets"], blobs["n_fg"], blobs["n_bg"], beta, *maps)
+
+
+class MaskLossFunction(Function):
+    """loss_mask of dtc_mask_loss over mask_logits [Rm,K,M,M]: forward is one loss-only call, backward one call that writes the dense
+    gradient with the incoming gradient as its device-side `upstream`."""
+    @staticmethod
+    def forward(ctx, mask_logits, masks, mask_class):
+        ctx.save_for_backward(mask_logits, masks, mask_class)
+        return hip_mask.mask_loss(mask_logits, masks, mask_class, grad=False)["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        mask_logits, masks, mask_class = ctx.saved_tensors
+        upstream = grad_loss.detach().to(torch.float32).reshape(1).contiguous()
+        return hip_mask.mask_loss(mask_logits, masks, mask_class, upstream=upstream)["grad_mask_logits"], None, None
+
+
+def mask_rcnn_loss(mask_logits, blobs):
+    """Detectron's loss_mask (class-specific SigmoidCrossEntropyLoss, normalised) on the blobs of mask_targets_batched: mask_logits
+    [B*Fm, K, M, M] PRE-sigmoid, one row per row of blobs['masks_int32'] [B,Fm,M*M] (padding rows included: their targets are -1)
+    -> a 0-dim device tensor, differentiable in mask_logits: the mean over the elements of channel mask_class_labels[r] whose
+    target is 0 or 1; 0 without one."""
+    masks, cls = blobs["masks_int32"], blobs["mask_class_labels"]
+    _require_cuda(mask_logits, masks, cls)
+    return MaskLossFunction.apply(_as_input(mask_logits), masks, cls)
 
 
 def cross_entropy(cls_score, labels):

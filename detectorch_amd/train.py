@@ -3,13 +3,16 @@ native pieces: the minibatch of sample_rois_batched, detector.forward_train (RoI
 losses (model.loss.fast_rcnn_losses) and ClippedSGD (gradient clipping + momentum SGD in one call); and the two steps that train the
 RPN models the project serves: rpn_train_step (RPN only -- stage 1 of alternating training -- C4 and FPN) and faster_rcnn_train_step
 (the joint approximate Faster R-CNN step on C4), on the anchor minibatch of rpn_targets_batched and the fused RPN losses
-(model.loss.rpn_losses).  The joint step on FPN, mask training and the dataset are not here."""
+(model.loss.rpn_losses); and mask_rcnn_train_step, the joint step of the C4 Mask R-CNN model: faster_rcnn_train_step plus the mask
+targets of mask_targets_batched (polygons rasterised on the device), detector.forward_train_mask on the shared features and the
+fused mask loss (model.loss.mask_rcnn_loss).  The joint step on FPN, keypoints and the dataset are not here."""
 import torch
 
 from . import hip
 from .model import loss as _loss
 from .model.roi_align import RoIAlign
 from .utils.fast_rcnn_sample_rois import sample_rois_batched
+from .utils.mask_rcnn_targets import mask_targets_batched
 from .utils.rpn_targets import rpn_targets_batched
 from .utils.solver import adjust_learning_rate, get_lr_at_iter
 
@@ -77,21 +80,18 @@ def rpn_train_step(model, optimizer, images, gt, it=None, **rpn_knobs):
     return loss_rpn_cls.detach(), loss_rpn_bbox.detach()
 
 
-def faster_rcnn_train_step(model, optimizer, images, gt, it=None, rpn_knobs=None, post_nms_top_n=2000, pre_nms_top_n=12000,
-                           **head_knobs):
-    """The joint approximate Faster R-CNN step on the C4 model (use_rpn_head=True, no FPN): RPN forward and losses; under no_grad,
-    the proposals of hip.generate_proposals with the training top-n (post-NMS <= 2048, the minibatch kernel's limit);
-    sample_rois_batched on those proposals and the gt, BOTH in blob coordinates with im_scale 1, so that `rois` needs no rescaling;
-    RoIAlign on the shared features, the res5 head and the two heads; fast_rcnn_losses; ONE backward of the four losses (the
-    proposals carry no gradient: "approximate"), optimizer.step().  gt: see _rpn_forward_losses, plus gt_classes i32 [B,G] and
-    optional rand_keys [B,G+P]; **head_knobs: the keywords of sample_rois_batched.
-    -> (loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, accuracy, blobs); nothing syncs with the host."""
+def _check_joint_c4(model, post_nms_top_n):
     if model.use_fpn_body:
         raise NotImplementedError("the joint step covers the C4 model: on FPN the sampled RoIs would have to be distributed over the "
                                   "levels for training")
     if post_nms_top_n < 1 or post_nms_top_n > 2048:
         raise ValueError("post_nms_top_n must be in 1 .. 2048 (the proposal rows of sample_rois_batched)")
-    _set_lr(optimizer, it)
+
+
+def _joint_c4_forward_losses(model, images, gt, rpn_knobs, post_nms_top_n, pre_nms_top_n, head_knobs):
+    """What the joint steps on the C4 model share, up to the backward: RPN forward and losses; under no_grad, the proposals and the
+    Fast R-CNN minibatch (both in blob coordinates); RoIAlign on the shared features, the res5 head and the two head losses.
+    -> (loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, accuracy, blobs, feats, gt_blob)."""
     cls_logits, bbox_pred, feats, _, loss_rpn_cls, loss_rpn_bbox = _rpn_forward_losses(model, images, gt, rpn_knobs or {})
     B, h, w = images.shape[0], images.shape[2], images.shape[3]
     with torch.no_grad():
@@ -111,7 +111,58 @@ def faster_rcnn_train_step(model, optimizer, images, gt, it=None, rpn_knobs=None
         feats, rois.reshape(-1, rois.shape[-1]))
     x = model._head(roi_features)
     loss_cls, loss_bbox, acc = _loss.fast_rcnn_losses(model.classif_head(x), model.bbox_head(x), blobs)
+    return loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, acc, blobs, feats, gt_blob
+
+
+def faster_rcnn_train_step(model, optimizer, images, gt, it=None, rpn_knobs=None, post_nms_top_n=2000, pre_nms_top_n=12000,
+                           **head_knobs):
+    """The joint approximate Faster R-CNN step on the C4 model (use_rpn_head=True, no FPN): RPN forward and losses; under no_grad,
+    the proposals of hip.generate_proposals with the training top-n (post-NMS <= 2048, the minibatch kernel's limit);
+    sample_rois_batched on those proposals and the gt, BOTH in blob coordinates with im_scale 1, so that `rois` needs no rescaling;
+    RoIAlign on the shared features, the res5 head and the two heads; fast_rcnn_losses; ONE backward of the four losses (the
+    proposals carry no gradient: "approximate"), optimizer.step().  gt: see _rpn_forward_losses, plus gt_classes i32 [B,G] and
+    optional rand_keys [B,G+P]; **head_knobs: the keywords of sample_rois_batched.
+    -> (loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, accuracy, blobs); nothing syncs with the host."""
+    _check_joint_c4(model, post_nms_top_n)
+    _set_lr(optimizer, it)
+    loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, acc, blobs, _, _ = _joint_c4_forward_losses(
+        model, images, gt, rpn_knobs, post_nms_top_n, pre_nms_top_n, head_knobs)
     optimizer.zero_grad()
     (loss_rpn_cls + loss_rpn_bbox + loss_cls + loss_bbox).backward()
     optimizer.step()
     return loss_rpn_cls.detach(), loss_rpn_bbox.detach(), loss_cls.detach(), loss_bbox.detach(), acc, blobs
+
+
+def mask_rcnn_train_step(model, optimizer, images, gt, it=None, rpn_knobs=None, post_nms_top_n=2000, pre_nms_top_n=12000,
+                         **head_knobs):
+    """The joint approximate Mask R-CNN step on the C4 model (use_rpn_head=True, use_mask_head=True with the 'upshare' head, no FPN):
+    everything faster_rcnn_train_step does up to its backward, then, under no_grad, mask_targets_batched at M = 14 on the minibatch
+    (the polygons, like the gt boxes, in blob coordinates with im_scale 1, so that mask_rois are the foreground rows of `rois` bit
+    for bit); detector.forward_train_mask on the shared features; mask_rcnn_loss; ONE backward of the five losses,
+    optimizer.step().  gt: as for faster_rcnn_train_step, plus poly_xy f32 [B,PTS,2], poly_ptr i32 [B,NP+1], gt_poly_ptr i32 [B,G+1]
+    (utils.mask_rcnn_targets.pack_polygons) in ORIGINAL image coordinates like gt_boxes.
+    -> (loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, loss_mask, accuracy, blobs) with the mask blobs merged into blobs; nothing
+    syncs with the host."""
+    if not getattr(model, "use_mask_head", False):
+        raise NotImplementedError("mask_rcnn_train_step takes a model with use_mask_head=True")
+    _check_joint_c4(model, post_nms_top_n)
+    _set_lr(optimizer, it)
+    loss_rpn_cls, loss_rpn_bbox, loss_cls, loss_bbox, acc, blobs, feats, gt_blob = _joint_c4_forward_losses(
+        model, images, gt, rpn_knobs, post_nms_top_n, pre_nms_top_n, head_knobs)
+    B = images.shape[0]
+    # the mask rows per image: the foreground quota of the minibatch (hip_train.train_params: half to even), so no row is cut
+    quota = int(round(head_knobs.get("fg_fraction", 0.25) * head_knobs.get("rois_per_image", 512)))
+    with torch.no_grad():
+        poly_blob = (gt["poly_xy"] * gt["im_scale"].reshape(B, 1, 1)).contiguous()   # one float32 multiply, as gt_blob
+        mb = mask_targets_batched(blobs, blobs["proposals"], gt_blob, gt["gt_classes"], gt["gt_is_crowd"], gt["gt_counts"],
+                                  torch.ones_like(gt["im_scale"]), (poly_blob, gt["poly_ptr"], gt["gt_poly_ptr"]),
+                                  M=model.mask_head.roi_height, k_min=0, k_max=0, mask_rows=min(max(quota, 1), 512))   # M: res5 halves, the
+        # transposed conv doubles: 14
+    mask_rois = mb["mask_rois"]
+    mask_logits = model.forward_train_mask(feats, mask_rois.reshape(-1, 5))
+    loss_mask = _loss.mask_rcnn_loss(mask_logits, mb)
+    blobs.update({k: v for k, v in mb.items() if k != "_raw"})
+    optimizer.zero_grad()
+    (loss_rpn_cls + loss_rpn_bbox + loss_cls + loss_bbox + loss_mask).backward()
+    optimizer.step()
+    return (loss_rpn_cls.detach(), loss_rpn_bbox.detach(), loss_cls.detach(), loss_bbox.detach(), loss_mask.detach(), acc, blobs)
