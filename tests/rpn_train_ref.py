@@ -83,17 +83,27 @@ def make_case(name):
     im_hw (h, w), rand_keys u32 [N])."""
     if name == "hand":
         return hand_case()
-    spec, G, n_crowd, (im_h, im_w), im_scale, _, seed = CASES[name]
+    spec, G, n_crowd, im_hw, im_scale, _, seed = CASES[name]
+    return seeded_case(spec, G, n_crowd, im_hw, im_scale, seed, JITTER.get(name, 0.12))
+
+
+def seeded_case(spec, G, n_crowd, im_hw, im_scale, seed, jit=0.12, keys=None, pick=None):
+    """make_case's construction for any spec.  keys: None (uniform uint32) or an array [N]; pick: the anchors the gt are jittered
+    copies of (None: drawn among those inside the image)."""
+    im_h, im_w = im_hw
     rs = np.random.RandomState(20261019 + seed)
     anchors = anchors_of(spec)
     N = len(anchors)
-    keys = rs.randint(0, 2 ** 32, N, dtype=np.uint64).astype(np.uint32)
-    ok = np.where((anchors[:, 0] >= 0) & (anchors[:, 1] >= 0) & (anchors[:, 2] < im_w) & (anchors[:, 3] < im_h))[0]
-    pick = rs.choice(ok if len(ok) >= G else np.arange(N), G, replace=len(ok) < G)
-    src = anchors[pick].astype(np.float64)
+    if keys is None:
+        keys = rs.randint(0, 2 ** 32, N, dtype=np.uint64).astype(np.uint32)
+    if pick is None:
+        ok = np.where((anchors[:, 0] >= 0) & (anchors[:, 1] >= 0) & (anchors[:, 2] < im_w) & (anchors[:, 3] < im_h))[0]
+        pick = rs.choice(ok if len(ok) >= G else np.arange(N), G, replace=len(ok) < G)
+    src = anchors[np.asarray(pick)].astype(np.float64)
     size = np.tile(src[:, 2:] - src[:, :2] + 1.0, 2)
-    jit = JITTER.get(name, 0.12)
     gt = src + rs.uniform(-jit, jit, (G, 4)) * size                          # jittered anchors: fg and near-fg around each
+    keys = np.ascontiguousarray(keys).astype(np.uint32)
+    assert keys.shape == (N,)
     gt[:, 2:] = np.maximum(gt[:, 2:], gt[:, :2] + 1.0)
     if G > 2:
         gt[G - 1] = [im_w * 0.25, im_h * 0.25, im_w * 0.75, im_h * 0.75]    # one large box: a low-quality best anchor
@@ -230,6 +240,124 @@ def expanded(spec, labels, fg_index, fg_targets, n_fg, n_bg):
     return bt, bi, bo
 
 
+# ---- where the selection cuts: bookkeeping of the cases below --------------------------------------------------------------------
+KEY_FIELDS = ((44, 52), (33, 44), (22, 33), (11, 22), (0, 11))     # of (rand_key << 20) | index: the bin, then the four 11-bit digits
+
+
+def selection_profile(case, params, m=None):
+    """From minibatch() alone, per group -> {"fg" / "bg": dict(candidates, taken, bin_population: the candidates whose rand_key >> 24
+    is that of the last taken key (0: none taken), cuts, bit: the highest bit in which the last taken and the first not-taken 52-bit
+    key differ, field: the KEY_FIELDS entry that holds it (both None unless the selection cuts), equal_rand_key: those two anchors
+    share their rand_key, max_index: the largest taken index (-1: none))}"""
+    m = minibatch(case, params) if m is None else m
+    rand = np.asarray(case["rand_keys"], np.uint32).astype(np.uint64)
+    key = (rand << np.uint64(20)) | np.arange(len(rand), dtype=np.uint64)
+    out = {}
+    for name, group, label in (("fg", m["fg"], 1), ("bg", m["bg"], 0)):
+        taken = group & (m["labels"] == label)
+        left = group & ~taken
+        p = dict(candidates=int(group.sum()), taken=int(taken.sum()), bin_population=0, cuts=bool(taken.any() and left.any()), bit=None,
+                 field=None, equal_rand_key=False, max_index=int(np.where(taken)[0].max(initial=-1)))
+        if taken.any():
+            last = int(key[taken].max())
+            p["bin_population"] = int((rand[group] >> np.uint64(24) == np.uint64(last >> 44)).sum())
+            if left.any():
+                first = int(key[left].min())
+                assert first > last
+                p["bit"] = (last ^ first).bit_length() - 1
+                p["field"] = [f for f in KEY_FIELDS if f[0] <= p["bit"] < f[1]][0]
+                p["equal_rand_key"] = last >> 20 == first >> 20
+        out[name] = p
+    return out
+
+
+# ---- past the sizes and key patterns of CASES: clustered keys, large quotas, the 65 536 switch, 2^20 anchors, a large batch ------
+# (tests/README_rpn_train.md, (h) - (k); tests/test_rpn_train_host.py asserts what each of them is there for)
+def _rs(seed):
+    return np.random.RandomState(20261019 + 2000 + seed)
+
+
+CLUSTER_PARAMS = dict(batch_size_per_im=64, straddle_thresh=-1.0)
+# name -> keys of N anchors.  The digit sets put 11 random bits (2048 values for ~2500 candidates: neighbours in key order differ in
+# their low bits) where one field of the 52-bit key is; their seeds are the first at which that field decides for the bg group.
+KEY_SETS = {
+    "arange": lambda N: np.arange(N), "constant": lambda N: np.full(N, 0x5A5A5A5A), "reversed": lambda N: N - 1 - np.arange(N),
+    "three": lambda N: _rs(1).randint(0, 3, N), "own_bin": lambda N: (np.arange(N, dtype=np.uint64) << np.uint64(24)) & np.uint64(0xFFFFFFFF),
+    "digit_bin": lambda N: _rs(DIGIT_SEEDS["digit_bin"]).randint(0, 256, N).astype(np.uint64) << np.uint64(24),
+    "digit_33": lambda N: _rs(DIGIT_SEEDS["digit_33"]).randint(0, 2048, N) << 13,
+    "digit_22": lambda N: _rs(DIGIT_SEEDS["digit_22"]).randint(0, 2048, N) << 2,
+    "digit_11": lambda N: _rs(DIGIT_SEEDS["digit_11"]).randint(0, 8192, N),
+    "digit_index": lambda N: _rs(DIGIT_SEEDS["digit_index"]).randint(0, 4, N),
+}
+DIGIT_SEEDS = {"digit_bin": 0, "digit_33": 0, "digit_22": 0, "digit_11": 1, "digit_index": 0}
+CLUSTER_SETS = ("arange", "constant", "reversed", "three", "own_bin")
+DIGIT_FIELDS = {"digit_bin": (44, 52), "digit_33": (33, 44), "digit_22": (22, 33), "digit_11": (11, 22), "digit_index": (0, 11)}
+
+
+def keys_of(name, N):
+    return np.ascontiguousarray(KEY_SETS[name](N)).astype(np.uint32)
+
+
+def cluster_case(keys, gt_seed=11):
+    """one level of 5 anchors on 16 x 32 (N = 2560), 3 gt, every anchor inside: about 2547 bg candidates for 61 places"""
+    spec = single(5, 16, 32)
+    return seeded_case(spec, 3, 0, (256, 512), 1.0, gt_seed, keys=keys_of(keys, 2560))
+
+
+QUOTA_PARAMS = {   # name -> (batch_size_per_im, fg_fraction, positive_overlap = negative_overlap, gt count)
+    "quota_300": (600, 0.5, 0.0, 5), "quota_600": (1200, 0.5, 0.0, 5), "quota_2048": (4096, 0.5, 0.0, 5), "quota_4096": (4096, 1.0, 0.0, 5),
+    "quota_2050": (2050, 1.0, 0.0, 5), "quota_1025": (1025, 1.0, 0.0, 5), "quota_129": (129, 1.0, 0.0, 5), "quota_bg": (4096, 1.0, 0.05, 5), "quota_no_gt": (4096, 1.0, 0.0, 0),
+    "quota_arange": (600, 0.5, 0.0, 5)}                                    # ... with arange keys: the whole FG group in one bin
+SWITCH_SHAPES = {65535: (15, 17, 257), 65536: (1, 256, 256), 65537: (1, 1, 65537)}
+
+
+def spec_2p20():
+    """16 anchors per cell on 256 x 256: N = 2^20, DTC_RPN_TRAIN_MAX_ANCHORS"""
+    return [(16, 256, 256, 16.0, np.vstack([base_anchors(15, 16), base_anchors(1, 16, size=16)]))]
+
+
+TARGET_CASES = tuple("cluster_" + k for k in CLUSTER_SETS) + ("c4_arange",) + tuple(DIGIT_FIELDS) + ("cluster_b3",) + tuple(QUOTA_PARAMS) + \
+    tuple("switch_%d" % n for n in SWITCH_SHAPES) + ("full_2p20", "batch_300")
+_BUILT = {}
+
+
+def target_case(name):
+    """-> (the images of one call: cases of one spec, parameter overrides); built once"""
+    if name not in _BUILT:
+        _BUILT[name] = _target_case(name)
+    return _BUILT[name]
+
+
+def _target_case(name):
+    if name.startswith("cluster_") and name[8:] in KEY_SETS:
+        return [cluster_case(name[8:])], CLUSTER_PARAMS
+    if name in DIGIT_FIELDS:
+        return [cluster_case(name)], CLUSTER_PARAMS
+    if name == "cluster_b3":                                               # three gt sets, three key sets
+        return [cluster_case("reversed", 12), cluster_case("digit_22", 13), cluster_case("three", 14)], CLUSTER_PARAMS
+    if name == "c4_arange":
+        return [dict(make_case("c4"), rand_keys=keys_of("arange", 28500))], CASES["c4"][5]
+    if name in QUOTA_PARAMS:
+        R, frac, thresh, count = QUOTA_PARAMS[name]
+        case = seeded_case(single(3, 32, 48), 5, 0, (512, 768), 1.0, 21, keys=keys_of("arange", 4608) if name == "quota_arange" else None)
+        return [dict(case, count=count)], dict(batch_size_per_im=R, fg_fraction=frac, positive_overlap=thresh, negative_overlap=thresh,
+                                               straddle_thresh=-1.0)
+    if name.startswith("switch_"):
+        n = int(name[7:])
+        A, H, W = SWITCH_SHAPES[n]
+        return [seeded_case(single(A, H, W), 3, 0, (H * 16, W * 16), 1.0, 31 + b) for b in range(2)], \
+            dict(batch_size_per_im=64, straddle_thresh=-1.0 if n == 65537 else 0.0)      # (a 1 x W map of 32-pixel anchors: none inside)
+    if name == "full_2p20":
+        # gt at anchors 2 and 12 of two cells (indices below and above 2^19); keys that favour high indices, 4096 anchors per value
+        N, at = 1 << 20, lambda a, h, w: (a * 256 + h) * 256 + w
+        return [seeded_case(spec_2p20(), 2, 0, (4096, 4096), 1.0, 41, keys=(N - 1 - np.arange(N)) >> 12,
+                            pick=[at(2, 100, 50), at(12, 200, 180)])], dict(straddle_thresh=-1.0)
+    if name == "batch_300":                                                # counts 0 .. 3 and keys differ from image to image
+        A, H, W = SIZE_SHAPES[63]
+        return [dict(seeded_case(single(A, H, W), 3, 0, (H * 16, W * 16), 1.0, 100 + b), count=b % 4) for b in range(300)], CASES["n63"][5]
+    raise KeyError(name)
+
+
 # ---- the losses: float64 yardsticks ------------------------------------------------------------------------------------------------
 def losses64(spec, cls, box, labels, fg_index, fg_targets, n_fg, n_bg, beta, upstream=(1.0, 1.0)):
     """cls / box: per level float32 [B,A,H,W] / [B,4A,H,W]; labels i32 [B,N]; fg_index [B,F]; fg_targets f32 [B,F,4]; n_fg, n_bg [B].
@@ -295,15 +423,18 @@ def make_loss_case(name, B=2, seed=0, logit_scale=3.0):
     """Seeded loss inputs on the maps of case `name` (the losses do not depend on how the labels came about): dict(spec, cls, box
     (lists of float32 arrays), labels [B,N] in {1, 0, -1}, fg_index [B,F] = the anchors labelled 1 in a random order, -1 behind,
     fg_targets [B,F,4], n_fg, n_bg [B])"""
-    spec = loss_spec(name)
-    N = count_anchors(spec)
-    F = LOSS_F.get(name, 16)
     rs = np.random.RandomState(20261019 + 1000 + seed + 7 * sorted(LOSS_CASES).index(name))
+    return loss_inputs(loss_spec(name), B, LOSS_F.get(name, 16), rs, logit_scale)
+
+
+def loss_inputs(spec, B, F, rs, logit_scale=3.0, fg_counts=None):
+    """make_loss_case's construction for any spec and F; fg_counts: n_fg per image (None: drawn)"""
+    N = count_anchors(spec)
     labels, fg_index = np.full((B, N), -1, np.int32), np.full((B, F), -1, np.int32)
     fg_targets, n_fg, n_bg = np.zeros((B, F, 4), np.float32), np.zeros(B, np.int32), np.zeros(B, np.int32)
     for b in range(B):
         perm = rs.permutation(N)
-        n_fg[b] = rs.randint(1 if b == 0 else 0, min(F, N) + 1)
+        n_fg[b] = rs.randint(1 if b == 0 else 0, min(F, N) + 1) if fg_counts is None else fg_counts[b]
         n_bg[b] = rs.randint(0, min(N - n_fg[b], 3 * F) + 1)
         labels[b, perm[:n_fg[b]]], labels[b, perm[n_fg[b]:n_fg[b] + n_bg[b]]] = 1, 0
         fg_index[b, :n_fg[b]] = perm[:n_fg[b]]
@@ -315,6 +446,52 @@ def make_loss_case(name, B=2, seed=0, logit_scale=3.0):
 
 def y_of(c, beta=1.0 / 9.0, upstream=(1.0, 1.0)):
     return losses64(c["spec"], c["cls"], c["box"], c["labels"], c["fg_index"], c["fg_targets"], c["n_fg"], c["n_bg"], beta, upstream)
+
+
+# ---- the losses past one round of each stride loop (tests/README_rpn_train.md; compared with y_of alone: e_ref = (0, 0)) -----------
+LOSS_DENSE_ROUND = 512 * 256                  # kRpnLossMaxBlocks workgroups of kLossThreads: the dense pass starts over above this N
+LOSS_BIG_SHAPES = {"n131071": [(1, 1, 131071)], "n131072": [(1, 1, 131072)], "n131073": [(1, 1, 131073)],
+                   "two_level": [(1, 1, 131075), (3, 5, 7)]}
+LOSS_BIG_CASES = tuple(LOSS_BIG_SHAPES) + ("rows_4096", "rows_300", "batch_257", "batch_600")
+
+
+def big_loss_case(name):
+    """-> the inputs of make_loss_case's form; built once"""
+    if ("loss", name) not in _BUILT:
+        _BUILT["loss", name] = _big_loss_case(name)
+    return _BUILT["loss", name]
+
+
+def _big_loss_case(name):
+    rs = _rs(500 + LOSS_BIG_CASES.index(name))
+    if name in LOSS_BIG_SHAPES:
+        spec = [lv for s in LOSS_BIG_SHAPES[name] for lv in single(*s)]
+        c = loss_inputs(spec, 2, 16, rs, fg_counts=[16, 9])
+        if name == "two_level":                                            # four counted rows of each image lie in the second level
+            off = offsets(spec)
+            for b in range(2):
+                new = off[1] + rs.choice(off[2] - off[1], 4, replace=False)
+                c["labels"][b, c["fg_index"][b, :4]] = -1
+                c["labels"][b, new], c["fg_index"][b, :4] = 1, new
+                c["n_bg"][b] = int((c["labels"][b] == 0).sum())
+        return c
+    if name == "rows_4096":                                                # F = DTC_RPN_TRAIN_MAX_BATCH_PER_IM on N = 4608
+        N = 4608
+        c = loss_inputs(single(3, 32, 48), 2, 4096, rs, fg_counts=[4096, 2500])
+        c["fg_index"][1, [5, 1000, 2499]] = [-1, N, 2 ** 30]               # garbage in counted rows: skipped
+        free = np.where(c["labels"][1] != 1)[0]                            # past n_fg: real anchors, garbage and arbitrary targets
+        c["fg_index"][1, 2500:] = np.r_[rs.choice(free, 4096 - 2500 - 3, replace=False), -7, N + 1, 2 ** 31 - 1]
+        c["fg_targets"][1, 2500:] = rs.standard_normal((4096 - 2500, 4)).astype(np.float32) * 1e3
+        return c
+    if name == "rows_300":                                                 # B F = 900: three rounds of 256 rows and a part of a fourth
+        return loss_inputs(single(3, 32, 48), 3, 300, rs, fg_counts=[300, 17, 300])
+    B = int(name[6:])                                                      # batch_257, batch_600: counts below 0 and above F
+    spec, F = single(1, 2, 2), 2
+    c = loss_inputs(spec, B, F, rs, fg_counts=[2] * B)
+    c["labels"] = rs.randint(-1, 2, (B, 4)).astype(np.int32)
+    c["n_fg"], c["n_bg"] = rs.randint(-2, 6, B).astype(np.int32), rs.randint(-3, 5, B).astype(np.int32)
+    c["n_fg"][-1], c["n_bg"][-1] = 5, 3                                    # the last image counts (n_fg clamped to F)
+    return c
 
 
 def sample_rows(name, n, k=2000):

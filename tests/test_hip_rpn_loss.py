@@ -192,15 +192,13 @@ def test_upstream_and_loss_only():
             assert (got[k] is None) if not on else all(rr.same_bits(a, b) for a, b in zip(got[k], base[k]))
 
 
-def test_repeat_and_capture_at_full_size(g):
+def repeat_and_capture(c):
+    """two eager calls and two graph replays over outputs and workspace refilled with 0xFF, bit-identical -> (the first, B, N)"""
     from detectorch_amd import hip_rpn
-    name = "fpn"
-    c = rr.make_loss_case(name)
     f32, i32 = torch.float32, torch.int32
     cls, box = [dev(x, f32) for x in c["cls"]], [dev(x, f32) for x in c["box"]]
     gc, gb = [torch.empty_like(x) for x in cls], [torch.empty_like(x) for x in box]
     levels, B, N = hip_rpn.map_levels(cls, box, gc, gb)
-    assert (B, N) == (2, 121515)
     args = [dev(c["labels"], i32), dev(c["fg_index"], i32), dev(c["fg_targets"], f32), dev(c["n_fg"], i32), dev(c["n_bg"], i32)]
     out = hip_rpn.loss_outputs(levels, B, "cuda")
     snap = lambda: [out["losses"].cpu().numpy().copy(), out["n_valid"].cpu().numpy().copy()] + [t.cpu().numpy().copy() for t in gc + gb]
@@ -227,9 +225,51 @@ def test_repeat_and_capture_at_full_size(g):
         runs.append(snap())
     for other in runs[1:]:
         assert all(rr.same_bits(a, b) for a, b in zip(runs[0], other))
-    got = dict(losses=runs[0][0], n_valid=int(runs[0][1][0]), grad_cls=runs[0][2:2 + len(gc)], grad_box=runs[0][2 + len(gc):])
+    return dict(losses=runs[0][0], n_valid=int(runs[0][1][0]), grad_cls=runs[0][2:2 + len(gc)], grad_box=runs[0][2 + len(gc):]), B, N
+
+
+def test_repeat_and_capture_at_full_size(g):
+    c = rr.make_loss_case("fpn")
+    got, B, N = repeat_and_capture(c)
+    assert (B, N) == (2, 121515)
     e_ref = (float(g["loss_fpn_e_ref_cls"]), float(g["loss_fpn_e_ref_box"]))
     compare(got, c, e_ref=e_ref, what="fpn, B = 2")
+
+
+# ---- past one round of each stride loop (rr.LOSS_BIG_CASES): against the float64 yardstick alone, e_ref = (0, 0) ----------------------
+@pytest.mark.parametrize("name", sorted(rr.LOSS_BIG_SHAPES))
+def test_dense_pass_past_one_round(name):
+    c = rr.big_loss_case(name)
+    compare(run_loss(c), c, what=name)
+
+
+@pytest.mark.parametrize("name", ["rows_4096", "rows_300"])
+def test_fg_rows_past_one_round(name):
+    c = rr.big_loss_case(name)
+    got = run_loss(c)
+    compare(got, c, what=name)
+    if name == "rows_4096":                                                     # the anchors named past n_fg have no gradient
+        past = c["fg_index"][1, 2500:-3]
+        assert not got["grad_box"][0][1].reshape(3, 4, 32 * 48)[past // (32 * 48), :, past % (32 * 48)].any()
+        assert got["n_valid"] == 4096 + 2500 + int(c["n_bg"].sum())
+
+
+@pytest.mark.parametrize("name", ["batch_257", "batch_600"])
+def test_large_batches_and_clamped_counts(name):
+    c = rr.big_loss_case(name)
+    got = run_loss(c)
+    compare(got, c, what=name)
+    F = c["fg_index"].shape[1]
+    assert got["n_valid"] == int((np.clip(c["n_fg"].astype(np.int64), 0, F) + np.maximum(c["n_bg"].astype(np.int64), 0)).sum())
+
+
+def test_repeat_capture_and_loss_only_past_one_round():
+    c = rr.big_loss_case("two_level")
+    got, B, N = repeat_and_capture(c)
+    assert B == 2 and N > rr.LOSS_DENSE_ROUND
+    compare(got, c, what="two_level, repeated and replayed")
+    only = run_loss(c, g_cls=False, g_box=False)
+    assert rr.same_bits(only["losses"], got["losses"]) and only["n_valid"] == got["n_valid"]
 
 
 def test_rpn_losses_autograd():

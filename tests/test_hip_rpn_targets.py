@@ -287,3 +287,86 @@ def test_bad_argument_sets_write_nothing():
         for k, full in guards.items():
             assert bool((full == -1).all()), (kw, nulls, k)
         assert bool((out["workspace"] == 0xFF).all())
+
+
+# ---- (h) - (k): past the sizes and key patterns above (rr.TARGET_CASES; test_rpn_train_host.py asserts what each one reaches) --------
+WORST_ULPS = {}
+
+
+def run_case(g, name):
+    """every image of rr.target_case(name) in ONE call against its restatement -> (outputs, cases, params)"""
+    cases, params = rr.target_case(name)
+    got = run(cases, params)
+    for b, c in enumerate(cases):
+        WORST_ULPS[name] = max(WORST_ULPS.get(name, 0.0), check(got, b, c, params, e_ref=float(g["e_ref"])))
+    return got, cases, params
+
+
+def key_order(case, idx):
+    """the 52-bit keys of the anchors idx"""
+    return (case["rand_keys"].astype(np.uint64)[idx] << np.uint64(20)) | idx.astype(np.uint64)
+
+
+# ---- (h) ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["cluster_" + k for k in rr.CLUSTER_SETS] + ["c4_arange"])
+def test_clustered_keys(g, name):
+    got, (case,), _ = run_case(g, name)
+    bg = np.where(got["labels"][0] == 0)[0]
+    if name in ("cluster_arange", "c4_arange"):                                               # the first bg candidates in index order
+        assert bg.max() < 2 * len(bg) + 200
+    if name == "cluster_reversed":
+        assert bg.min() > rr.count_anchors(case["spec"]) - 2 * len(bg) - 200
+
+
+@pytest.mark.parametrize("name", sorted(rr.DIGIT_FIELDS))
+def test_every_digit_decides(g, name):
+    run_case(g, name)
+
+
+def test_clustered_batch_of_three_equals_three_calls(g):
+    got, cases, params = run_case(g, "cluster_b3")
+    for b, c in enumerate(cases):
+        one = run([c], params, G=3)
+        for k in OUT_NAMES:
+            assert rr.same_bits(got[k][b], one[k][0]), (b, k)
+    assert len({got["labels"][b].tobytes() for b in range(3)}) == 3
+
+
+# ---- (i) ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(rr.QUOTA_PARAMS))
+def test_large_quotas_and_the_sort_branches(g, name):
+    got, (case,), params = run_case(g, name)
+    R, frac, thresh, count = rr.QUOTA_PARAMS[name]
+    n, F = int(got["n_fg"][0]), int(frac * R)
+    assert got["fg_index"].shape == (1, F) and n + int(got["n_bg"][0]) == (n if thresh == 0 else R)
+    rows = got["fg_index"][0, :n]
+    assert np.all(np.diff(key_order(case, rows).astype(np.int64)) > 0)                        # sampling order: ascending (key, index)
+    assert n == F or thresh > 0                                                               # every anchor is fg: the quota is met
+    if count == 0:
+        assert np.all(got["fg_gt"] == -1) and not got["fg_targets"].any() and not got["bbox_targets"].any()
+        assert int(got["bbox_inside_weights"].sum()) == 4 * n
+    else:
+        zero = got["max_overlaps"][0][rows] == 0                                              # fg whose best IoU is 0: the first gt
+        assert got["fg_gt"][0, :n].min() >= 0 and zero.any() == (thresh == 0) and np.all(got["fg_gt"][0, :n][zero] == 0)
+
+
+# ---- (j) ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["switch_%d" % n for n in rr.SWITCH_SHAPES])
+def test_group_switch_with_two_images(g, name):
+    got, cases, _ = run_case(g, name)
+    assert not rr.same_bits(got["labels"][0], got["labels"][1])
+
+
+def test_two_to_the_twenty_anchors(g):
+    got, (case,), _ = run_case(g, "full_2p20")
+    assert got["labels"].shape == (1, 1 << 20)
+    assert got["fg_index"][0].max() >= 1 << 19 and np.where(got["labels"][0] == 0)[0].min() >= 1 << 19
+
+
+def test_batch_of_300(g):
+    got, cases, _ = run_case(g, "batch_300")
+    assert len(cases) == 300 and len({got["labels"][b].tobytes() for b in range(300)}) > 150
+
+
+def test_print_the_largest_dw_dh_distances():
+    print("largest dw / dh distance in ulps per case of (h) - (k): %s" % {k: round(v, 3) for k, v in WORST_ULPS.items()})

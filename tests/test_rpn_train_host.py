@@ -3,7 +3,8 @@
     tests/golden/make_rpn_train_golden.py): anchors, integers, overlaps as float32 bits, dx and dy bit for bit, dw and dh within
     e_ref + 2 float32 ulps of log(float64(ratio)) -- the rule of tests/README_train_targets.md; the float64 loss yardsticks
     against torch's and the reference's own float64 chain;
-  * every condition the cases of tests/README_rpn_train.md name actually occurs;
+  * every condition the cases of tests/README_rpn_train.md name actually occurs -- for the large and clustered cases (rr.TARGET_CASES,
+    rr.LOSS_BIG_CASES) through rr.selection_profile, with the thresholds of the kernels read from the source text;
   * libdetectorch_rpn_hip.so exports exactly what include/detectorch_rpn_hip.h declares and hip_rpn.SIGNATURES binds it, parameter
     names in order; the other five libraries' export lists are unchanged;
   * the return codes of both entries on bad arguments, in the order shapes, limits, pointers, workspace (validation precedes every
@@ -100,6 +101,133 @@ def test_cases_are_the_engineered_ones(g, mb):
     # below negative_overlap
     assert np.any(mb["c4"]["fg"] & (mb["c4"]["max_overlaps"] < 0.7)) and np.any(mb["fpn"]["fg"] & (mb["fpn"]["max_overlaps"] < 0.7))
     assert np.any(mb["n1024"]["fg"] & (mb["n1024"]["max_overlaps"] < 0.3))
+
+
+@pytest.fixture(scope="module")
+def profiles():
+    """rr.selection_profile and the restatement of every image of every case of rr.TARGET_CASES"""
+    out = {}
+    for name in rr.TARGET_CASES:
+        cases, params = rr.target_case(name)
+        p = dict(rr.DEFAULTS, **params)
+        ms = [rr.minibatch(c, p) for c in cases]
+        out[name] = [(rr.selection_profile(c, p, m), m) for c, m in zip(cases, ms)]
+    return out
+
+
+def sort_branch(n):
+    """the branch of block_bitonic_sort<1024> (csrc/block_sort.h) that sorts n taken fg keys"""
+    np2 = 2
+    while np2 < n:
+        np2 *= 2
+    per = (np2 + rr.SELECT_BLOCK - 1) // rr.SELECT_BLOCK
+    return ("merge", np2) if per <= 1 and np2 >= 256 else ("network, %d per thread" % per, np2)
+
+
+def test_large_and_clustered_cases_are_the_engineered_ones(profiles, mb):
+    from detectorch_amd import hip_rpn
+    src = lambda *parts: open(os.path.join(ROOT, "detectorch_amd", "csrc", *parts)).read()
+    text = src("rpn_train", "rpn_train_common.h") + src("rpn_train", "rpn_targets.hip") + src("rpn_train", "rpn_loss.hip")
+    const = lambda name, t=text: int(re.search(r"constexpr int %s = (\d+);" % name, t).group(1))
+    # the points the cases are placed round, from the source text
+    assert const("kRpnSelThreads") == rr.SELECT_BLOCK == 1024 and const("kRpnThreads") == rr.BLOCK == 256
+    assert re.search(r"for \(int e = tid; e < n_c; e \+= kRpnSelThreads\)", text)                # rpn_threshold strides by its workgroup
+    assert const("kRpnGroupPer") * const("kRpnThreads") == 2048 and re.search(r"constexpr int kRpnGroupPerFrom = 1 << 16;", text)
+    assert const("kRpnLossMaxBlocks") * const("kLossThreads", src("loss", "loss_common.h")) == rr.LOSS_DENSE_ROUND == 131072
+    assert hip_rpn.LOSS_BLOCK == 256 and hip_rpn.MAX_ANCHORS == 1 << 20 and hip_rpn.MAX_BATCH_PER_IM == 4096
+    header = open(os.path.join(ROOT, "include", "detectorch_rpn_hip.h")).read()
+    assert re.search(r"#define DTC_RPN_TRAIN_MAX_ANCHORS \(?1 << 20\)?", header) and re.search(r"#define DTC_RPN_TRAIN_MAX_BATCH_PER_IM 4096", header)
+    assert re.search(r"if \(per <= 1 && n_pow2 >= 256\) block_merge_sort_e1<THREADS>", src("block_sort.h"))
+    assert re.search(r"block_bitonic_sort<kRpnSelThreads>\(keys, np2\)", text)
+    assert const("kRpnIdxBits") == 20 and const("kRpnDigitBits") == 11 and rr.KEY_FIELDS == ((44, 52), (33, 44), (22, 33), (11, 22), (0, 11))
+    # what the earlier cases reach: a threshold bin of some hundred candidates, at most 128 fg to sort, anchor indices below 2^17
+    old = {c: rr.selection_profile(rr.make_case(c), rr.params_of(c), mb[c]) for c in ("fpn5", "c4", "fpn")}
+    assert max(p[s]["bin_population"] for p in old.values() for s in ("fg", "bg")) < 1024
+    assert max(p["fg"]["taken"] for p in old.values()) == 128 and sort_branch(128) == ("network, 1 per thread", 128)
+    assert max(p[s]["max_index"] for p in old.values() for s in ("fg", "bg")) < 1 << 17
+
+    one = lambda name: profiles[name][0][0]
+    # (h) clustered keys: the whole bg group in the threshold bin, more than one round of rpn_threshold's workgroup
+    for k in ("arange", "constant", "reversed", "three"):
+        p = one("cluster_" + k)
+        assert rr.count_anchors(rr.target_case("cluster_" + k)[0][0]["spec"]) == 2560
+        assert p["bg"]["cuts"] and p["bg"]["candidates"] > 2300 and p["bg"]["taken"] == 64 - p["fg"]["taken"] > 32
+        assert p["bg"]["bin_population"] == p["bg"]["candidates"] > 2 * 1024, k
+    assert one("cluster_constant")["bg"]["equal_rand_key"] and one("cluster_three")["bg"]["equal_rand_key"]
+    keys = rr.target_case("cluster_own_bin")[0][0]["rand_keys"]
+    assert len(set((keys >> 24).tolist())) == 256 and not (keys & 0xFFFFFF).any() and one("cluster_own_bin")["bg"]["bin_population"] <= 10
+    assert one("c4_arange")["bg"]["bin_population"] == one("c4_arange")["bg"]["candidates"] > 3 * 4096
+    # every field of the key decides once; in one case two anchors with one rand_key straddle the boundary
+    for name, field in rr.DIGIT_FIELDS.items():
+        assert one(name)["bg"]["cuts"] and one(name)["bg"]["field"] == field, name
+    assert sorted(rr.DIGIT_FIELDS.values()) == sorted(rr.KEY_FIELDS)
+    assert one("digit_index")["bg"]["equal_rand_key"] and not any(one(n)["bg"]["equal_rand_key"] for n in rr.DIGIT_FIELDS if n != "digit_index")
+    assert all(one(n)["bg"]["bin_population"] > 2 * 1024 for n in rr.DIGIT_FIELDS if n != "digit_bin")
+    b3 = rr.target_case("cluster_b3")[0]
+    assert len(b3) == 3 and all(p["bg"]["bin_population"] > 2 * 1024 for p, _ in profiles["cluster_b3"])
+    assert len({c["rand_keys"].tobytes() for c in b3}) == 3 and len({c["gt_boxes"].tobytes() for c in b3}) == 3
+    # (i) every anchor fg: the quota is what is sorted -- the merge sort at 256, 512 and 1024 keys, two and four keys per thread,
+    # counts that are no power of two just above each edge, fgkeys full
+    taken = {n: one(n)["fg"]["taken"] for n in rr.QUOTA_PARAMS}
+    assert taken == dict(quota_300=300, quota_600=600, quota_2048=2048, quota_4096=4096, quota_2050=2050, quota_1025=1025, quota_129=129,
+                         quota_bg=taken["quota_bg"], quota_no_gt=4096, quota_arange=300)
+    assert one("quota_arange")["fg"]["bin_population"] == 4608 > 4 * 1024                     # the fg half of the candidate list, strided
+    assert [sort_branch(taken[n]) for n in ("quota_129", "quota_300", "quota_600", "quota_1025", "quota_2048", "quota_2050", "quota_4096")] == \
+        [("merge", 256), ("merge", 512), ("merge", 1024), ("network, 2 per thread", 2048), ("network, 2 per thread", 2048),
+         ("network, 4 per thread", 4096), ("network, 4 per thread", 4096)]
+    for n in rr.QUOTA_PARAMS:
+        (p, m), (case, prm) = profiles[n][0], (rr.target_case(n)[0][0], rr.target_case(n)[1])
+        assert rr.count_anchors(case["spec"]) == 4608 and prm["straddle_thresh"] == -1.0 and m["inside"].all()
+        if n != "quota_bg":
+            assert p["fg"]["candidates"] == 4608 and p["fg"]["cuts"] and p["bg"]["candidates"] == 0
+            assert np.any(m["max_overlaps"][m["fg_index"][:m["n_fg"]]] == 0)                   # fg whose best IoU is 0
+            assert np.all(m["fg_gt"][:m["n_fg"]] >= 0) == (n != "quota_no_gt")
+    assert rr.target_case("quota_no_gt")[0][0]["count"] == 0 and np.all(profiles["quota_no_gt"][0][1]["fg_gt"] == -1)
+    p = one("quota_bg")                                                                       # fewer fg than F: the bg quota is R - n_fg
+    assert p["fg"]["taken"] == p["fg"]["candidates"] < 4096 and p["bg"]["taken"] == 4096 - p["fg"]["taken"] > 3000 and p["bg"]["cuts"]
+    # (j) round the switch of rpn_group to 2048 anchors per workgroup: the last workgroup is partial below and above it
+    for n, shape in rr.SWITCH_SHAPES.items():
+        cases = rr.target_case("switch_%d" % n)[0]
+        assert rr.count_anchors(cases[0]["spec"]) == n == shape[0] * shape[1] * shape[2] and len(cases) == 2
+        assert not np.array_equal(cases[0]["gt_boxes"], cases[1]["gt_boxes"]) and not np.array_equal(cases[0]["rand_keys"], cases[1]["rand_keys"])
+        for p, m in profiles["switch_%d" % n]:
+            assert p["fg"]["taken"] >= 1 and p["bg"]["cuts"] and p["fg"]["taken"] + p["bg"]["taken"] == 64
+    assert sorted(rr.SWITCH_SHAPES) == [(1 << 16) - 1, 1 << 16, (1 << 16) + 1] and 65537 % 2048 == 1
+    (p, m), case = profiles["full_2p20"][0], rr.target_case("full_2p20")[0][0]
+    assert rr.count_anchors(case["spec"]) == 1 << 20 == hip_rpn.MAX_ANCHORS and case["spec"][0][0] == hip_rpn.MAX_ANCHORS_PER_CELL
+    assert p["fg"]["max_index"] >= 1 << 19 and np.where(m["labels"] == 0)[0].min() >= 1 << 19   # index bits 17 - 19 in taken anchors
+    assert p["bg"]["cuts"] and p["bg"]["equal_rand_key"] and p["bg"]["bin_population"] == p["bg"]["candidates"] > 10 ** 6
+    assert m["fg_index"][:m["n_fg"]].min() < 1 << 19 and p["fg"]["taken"] + p["bg"]["taken"] == 256
+    cases = rr.target_case("batch_300")[0]
+    assert len(cases) == 300 > rr.BLOCK and sorted({c["count"] for c in cases}) == [0, 1, 2, 3]
+    assert len({c["rand_keys"].tobytes() for c in cases}) == 300 and len({m["labels"].tobytes() for _, m in profiles["batch_300"]}) > 150
+    # the losses: the dense pass starts over above 512 x 256 anchors, the rows above 256, the count above 256 images
+    n_of = lambda name: rr.count_anchors(rr.big_loss_case(name)["spec"])
+    assert [n_of("n%d" % n) for n in (131071, 131072, 131073)] == [131071, 131072, 131073]
+    c = rr.big_loss_case("two_level")
+    off = rr.offsets(c["spec"])
+    assert len(c["spec"]) == 2 and off[1] > rr.LOSS_DENSE_ROUND
+    for name in rr.LOSS_BIG_CASES:                                                            # no anchor has two counted rows
+        c = rr.big_loss_case(name)
+        B, F = c["fg_index"].shape
+        for b in range(B):
+            rows = c["fg_index"][b, :min(max(int(c["n_fg"][b]), 0), F)]
+            rows = rows[(rows >= 0) & (rows < n_of(name))]
+            assert len(set(rows.tolist())) == len(rows), name
+            if name == "two_level":
+                assert (rows >= off[1]).sum() == 4 and (rows < off[1]).sum() >= 5 and np.all(c["labels"][b, rows] == 1)
+    c = rr.big_loss_case("rows_4096")
+    assert c["fg_index"].shape == (2, hip_rpn.MAX_BATCH_PER_IM) and c["n_fg"].tolist() == [4096, 2500] and n_of("rows_4096") == 4608
+    assert c["fg_index"][1, [5, 1000, 2499]].tolist() == [-1, 4608, 2 ** 30] and np.all(c["fg_index"][0] >= 0)
+    past = c["fg_index"][1, 2500:]
+    assert ((past >= 0) & (past < 4608)).sum() > 1500 and c["fg_targets"][1, 2500:].all() and not (c["labels"][1][past[:-3]] == 1).any()
+    c = rr.big_loss_case("rows_300")
+    assert c["fg_index"].shape == (3, 300) and 900 % 256 and c["n_fg"].tolist() == [300, 17, 300]   # the last counted row is row 899
+    for B in (257, 600):
+        c = rr.big_loss_case("batch_%d" % B)
+        assert c["fg_index"].shape == (B, 2) and B > hip_rpn.LOSS_BLOCK and n_of("batch_%d" % B) == 4
+        assert c["n_fg"].min() < 0 and c["n_fg"].max() > 2 and c["n_bg"].min() < 0 and c["n_bg"].max() > 0
+        assert (c["n_fg"][256:] > 0).any() and (c["n_bg"][256:] > 0).any()                     # counts that matter past the first round
 
 
 def test_hand_made_case_conditions(mb):
