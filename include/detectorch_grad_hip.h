@@ -57,6 +57,11 @@ size_t dtc_roi_align_backward_workspace_bytes(int n_levels, int batch, int n_roi
  * element in the loop's order n, ph, pw, iy, ix, taps 1-4 -- the collapsed taps at the last row / column, where two taps of a
  * sample land on one pixel, included.  No atomics: every element is summed by ONE thread in that order, so the same inputs give
  * the same bits on every run, eagerly and under graph replay.  Denormal terms and sums are kept.
+ * A batch index is converted as the reference converts it, truncated toward zero: every value in (-1, 1) is image 0, 1.999 is
+ * image 1.  sampling_ratio <= 0, negative values included, is adaptive: ceil(roi size / pooled size) samples per bin and direction.
+ * A grad_output that is not finite propagates exactly as the reference's four-tap add does: a valid sample adds all four of its
+ * terms, the taps of weight zero included, so an infinite or NaN bin puts inf * 0 = NaN on the neighbouring pixels of its taps,
+ * and an element whose only terms are -0.0 holds 0.f + -0.0 = +0.0.  (The payload of such a NaN is not part of the contract.)
  * Bad RoIs contribute nothing and are never used as an index (the reference has undefined behaviour for them):
  *   - a batch index that truncates to a value outside [0, batch), or is not finite,
  *   - a level outside [0, n_levels),

@@ -79,14 +79,15 @@ def backward(top, rois, batch, height, width, scale, sampling_ratio, rows=None):
         b = int(rois[n, 0]) if cols == 5 else 0                                       # :105-109
         sw, sh, bin_w, bin_h, gh, gw, count = roi_geometry(rois[n, cols - 4:], scale, PH, PW, sampling_ratio)
         for ph in range(PH):                                                          # :100
-            ys = [axis(sh, bin_h, ph, iy, gh, height) for iy in range(gh)]
+            # an empty sample (:26-31, :176) adds nothing: dropped here, before the product of the two axes, in the loops' order
+            ys = [a for a in (axis(sh, bin_h, ph, iy, gh, height) for iy in range(gh)) if a[0]]
+            if not ys:
+                continue
             for pw in range(PW):                                                      # :99
                 t, t64 = top[n, :, ph, pw], top64[n, :, ph, pw]                       # :130-132
-                xs = [axis(sw, bin_w, pw, ix, gw, width) for ix in range(gw)]
+                xs = [a for a in (axis(sw, bin_w, pw, ix, gw, width) for ix in range(gw)) if a[0]]
                 for vy, y_lo, y_hi, ly, hy in ys:                                     # :144
                     for vx, x_lo, x_hi, lx, hx in xs:                                 # :148
-                        if not (vy and vx):                                           # :26-31, :176
-                            continue
                         ws = (F(hy * hx), F(hy * lx), F(ly * hx), F(ly * lx))         # :68
                         w64 = (float(hy) * float(hx), float(hy) * float(lx), float(ly) * float(hx), float(ly) * float(lx))
                         at = ((y_lo, x_lo), (y_lo, x_hi), (y_hi, x_lo), (y_hi, x_hi))  # :178-181
