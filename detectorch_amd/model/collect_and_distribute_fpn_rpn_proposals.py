@@ -11,6 +11,8 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..utils.fast_rcnn_sample_rois import sample_rois_batched
+from ..utils.multilevel_rois import roi_levels_batched
 
 
 class CollectAndDistributeFpnRpnProposals(torch.nn.Module):
@@ -32,6 +34,32 @@ class CollectAndDistributeFpnRpnProposals(torch.nn.Module):
             distr.append(by_level[p:p + int(c), :])
             p += int(c)
         return distr, res["idx_restore"][0, :n].cpu().numpy().astype(np.int64)
+
+
+def collect_sample_distribute(boxes, scores, counts, gt, *, post_nms_top_n=2000, k_min=2, k_max=5, rand_keys=None, **head_knobs):
+    """The training branch the reference left as Detectron's comment (:54-80, "TRAINING CODE BELOW NOT CONVERTED TO PYTORCH"), for a
+    batch and without a host sync: collect the top post_nms_top_n proposals by score over the RPN levels, add the gt boxes as
+    candidates and sample the minibatch with its labels and box targets (add_fast_rcnn_blobs), then distribute the SAMPLED rows over
+    the levels k_min .. k_max.
+      boxes f32 [B,L,P,4], scores f32 [B,L,P], counts i32 [B,L]: the per-level proposals of hip.generate_proposals (rows past the
+      counts are ignored); gt: dict of gt_boxes f32 [B,G,4], gt_classes / gt_is_crowd i32 [B,G], gt_counts i32 [B].  Everything is in
+      blob coordinates (im_scale 1), so that `rois` needs no rescaling.  rand_keys [B,G+post_nms_top_n] and **head_knobs: the keywords
+      of sample_rois_batched.
+    Each stage is an existing entry: hip.fpn_collect_distribute (only its rois5[..., 1:] and n_out are used: the levels of the
+    collected rows are not the levels of the sampled ones), sample_rois_batched(expanded=False), roi_levels_batched.
+    -> the dict of sample_rois_batched plus roi_levels i32 [B,R] (0 on padding rows), proposals f32 [B,T,4] (zeros past
+    proposal_counts) and proposal_counts i32 [B], T = post_nms_top_n."""
+    T = int(post_nms_top_n)
+    if T < 1 or T > 2048:
+        raise ValueError("post_nms_top_n must be in 1 .. 2048 (the proposal rows of sample_rois_batched)")
+    res = hip.fpn_collect_distribute(boxes, scores, counts, T, k_min, k_max)
+    proposals = res["rois5"][..., 1:].contiguous()
+    blobs = sample_rois_batched(proposals, res["n_out"], gt["gt_boxes"], gt["gt_classes"], gt["gt_is_crowd"], gt["gt_counts"],
+                                torch.ones((proposals.shape[0],), dtype=torch.float32, device=proposals.device), rand_keys=rand_keys,
+                                expanded=False, **head_knobs)
+    blobs["roi_levels"] = roi_levels_batched(blobs["rois"], blobs["n_rois"], k_min, k_max)
+    blobs["proposals"], blobs["proposal_counts"] = proposals, res["n_out"]
+    return blobs
 
 
 def collect_and_distribute(roi_list, roi_score_list, post_nms_topN, lvl_min, lvl_max):

@@ -18,7 +18,9 @@ Differences from the reference:
     kernels bench.py measures (detectorch_amd.pipeline.FpnRegionPath); `forward` stays the reference's batch-1 call;
   * `head_dtype=torch.bfloat16`: RoIAlign writes the pooled features in bf16 and fc6/fc7 run as bf16 MFMA GEMMs;
   * the constructor and forward() are inference only (the reference's README.md:3 scope); `forward_train(images, rois5)` is the
-    grad-enabled forward of the one configuration the reference trains (train_fast.py), see detectorch_amd/train.py.
+    grad-enabled forward of the one configuration the reference trains (train_fast.py) and of its FPN counterpart;
+    forward_train_rpn / forward_train_boxes / forward_train_mask are the grad-enabled branches of the joint steps, C4 and FPN:
+    see detectorch_amd/train.py.
 """
 import contextlib
 import pickle
@@ -30,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hip
+from ..utils.multilevel_rois import roi_levels_batched
 from .collect_and_distribute_fpn_rpn_proposals import CollectAndDistributeFpnRpnProposals
 from .generate_proposals import GenerateProposals
 from .roi_align import RoIAlign, RoIAlignFunction, preprocess_rois, roi_align_fpn
@@ -420,22 +423,51 @@ class detector(nn.Module):
 
     def forward_train(self, images, rois5):
         """The grad-enabled forward of the configuration the reference trains (train_fast.py:78-83, :134): the defaults of
-        detector(), R-50/101-C4 Fast R-CNN on given proposals.  images [B,3,H,W]; rois5 float32 [N,5] = (batch index, x1, y1, x2, y2)
+        detector(), R-50/101-C4 Fast R-CNN on given proposals -- and of its FPN counterpart (FPN body, two-layer MLP head, no RPN
+        head, no mask head: the model of demo_FPN.ipynb).  images [B,3,H,W]; rois5 float32 [N,5] = (batch index, x1, y1, x2, y2)
         in blob coordinates: the `rois` blob of sample_rois_batched viewed as rows, padding rows included (the losses ignore them).
-        conv_body -> RoIAlign with its native backward -> res5 head -> (cls_score [N,C] logits: no softmax, bbox_pred [N,4C]).
+        conv_body -> forward_train_boxes (C4: RoIAlign with its native backward -> res5 head; FPN: the levels of roi_levels_batched,
+        roi_align_fpn -> fc6 / fc7) -> (cls_score [N,C] logits: no softmax, bbox_pred [N,4C]).
         Anything else raises NotImplementedError; forward / forward_batched stay the inference entries."""
-        if (self.use_fpn_body or self.use_rpn_head or self.use_mask_head or self.use_two_layer_mlp_head or self.channels_last
+        if (self.use_fpn_body != self.use_two_layer_mlp_head or self.use_rpn_head or self.use_mask_head or self.channels_last
                 or getattr(self, "_optimized", False) or self.head_dtype not in (None, torch.float32)
                 or self.backbone_dtype not in (None, torch.float32)):
-            raise NotImplementedError("forward_train covers Fast R-CNN R-50/101-C4 on given proposals in float32 (the defaults of "
-                                      "detector())")
+            raise NotImplementedError("forward_train covers Fast R-CNN R-50/101-C4 (the defaults of detector()) and Fast R-CNN FPN with "
+                                      "the two-layer MLP head, on given proposals in float32")
         hip._require_cuda(images, rois5)
         if images.dim() != 4 or rois5.dim() != 2 or rois5.shape[1] != 5:
             raise ValueError("forward_train takes images [B,3,H,W] and rois5 [N,5] (batch index first)")
-        img_features = self.conv_body(images)
-        roi_features = RoIAlign(self.roi_height, self.roi_width, self.roi_spatial_scale, self.roi_sampling_ratio)(
-            img_features, rois5.detach().to(torch.float32).contiguous())
-        x = self._head(roi_features)
+        return self.forward_train_boxes(self.conv_body(images), rois5)
+
+    def roi_level_range(self):
+        """(k_min, k_max) of an FPN model: log2(1 / s) of the first and the last RoIAlign scale (2, 5 for 1/4 .. 1/32)."""
+        return int(log2(1 / self.roi_spatial_scale[0])), int(log2(1 / self.roi_spatial_scale[-1]))
+
+    def forward_train_boxes(self, img_features, rois5, roi_levels=None):
+        """The grad-enabled box branch on shared features, in float32, NCHW, not optimised -- the counterpart of forward_train_mask:
+        img_features as conv_body / forward_train_rpn returns them; rois5 float32 [N,5] = (batch index, x1, y1, x2, y2) in blob
+        coordinates: the `rois` blob of a minibatch viewed as rows, padding rows included (the losses ignore them).
+        C4: RoIAlign with its native backward -> conv_head.  FPN with the two-layer MLP head: roi_align_fpn on the first
+        len(roi_spatial_scale) maps (one launch forward, one call backward for all levels) with roi_levels int32 [N] (the roi_levels
+        blob; None: roi_levels_batched on rois5) -> fc6 / fc7.  -> (cls_score [N,C] logits: no softmax, bbox_pred [N,4C]).
+        Anything else raises NotImplementedError."""
+        if (self.use_fpn_body and not self.use_two_layer_mlp_head or self.channels_last or getattr(self, "_optimized", False)
+                or getattr(self, "_opt_dtype", None) is not None or self.head_dtype not in (None, torch.float32)
+                or self.backbone_dtype not in (None, torch.float32)):
+            raise NotImplementedError("forward_train_boxes covers the C4 models and the FPN models with the two-layer MLP head in "
+                                      "float32, NCHW, not optimised")
+        rois = rois5.detach().to(torch.float32).reshape(-1, 5).contiguous()
+        if not self.use_fpn_body:
+            hip._require_cuda(img_features, rois)
+            x = RoIAlign(self.roi_height, self.roi_width, self.roi_spatial_scale, self.roi_sampling_ratio)(img_features, rois)
+        else:
+            feats = list(img_features)[:len(self.roi_spatial_scale)]
+            hip._require_cuda(rois, roi_levels, *feats)
+            if roi_levels is None:
+                roi_levels = roi_levels_batched(rois, None, *self.roi_level_range())
+            x = roi_align_fpn(feats, self.roi_spatial_scale, rois, roi_levels.detach().to(torch.int32).reshape(-1).contiguous(),
+                              self.roi_height, self.roi_width, self.roi_sampling_ratio)
+        x = self._head(x)
         return self.classif_head(x), self.bbox_head(x)
 
     def forward_train_rpn(self, images):

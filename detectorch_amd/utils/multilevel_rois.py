@@ -33,6 +33,50 @@ def _run(rois, k_min, k_max):
     return (lv + k_min).astype(np.float32), per, restore
 
 
+MAX_ROWS = 2048          # rows per image of dtc_prepare_proposals
+
+
+def roi_levels_batched(rois, counts=None, k_min=2, k_max=5):
+    """The FPN level (index into k_min .. k_max) of arbitrary device rows, for training: map_rois_to_fpn_levels (:41-53) without the
+    numpy round trip and without a host sync.  rois float32 [B,R,4|5] or flat [N,4|5] on the GPU (the last four columns are the
+    box); counts int32 [B] or None (every row; flat input takes none).  -> int32 [B,R] / [N].
+    Decided by hip.prepare_proposals(im_scale = 1, dedup_scale = 0): every row kept in input order, the level from the one text of
+    the formula (csrc/fpn_map.h).  That entry takes at most 2048 rows per image: flat input is cut into groups of at most 2048 rows
+    (the mapping is per row, the grouping cannot change a level) and a batched R > 2048 is refused.  Level 0 goes to the rows past
+    counts[b], to all-zero rows (the padding of a minibatch: area 1) and to rows with a non-finite coordinate -- the entry DROPS
+    those, which would shift the rows behind them, so they go down as zeros."""
+    dev = hip._require_cuda(rois, counts)
+    if rois.dtype != torch.float32 or rois.dim() not in (2, 3) or rois.shape[-1] not in (4, 5):
+        raise TypeError("rois must be float32 [B,R,4|5] or [N,4|5]")
+    box = rois.detach()[..., -4:]
+    box = torch.where(torch.isfinite(box).all(-1, keepdim=True), box, torch.zeros((), dtype=box.dtype, device=dev))
+    if rois.dim() == 2:
+        if counts is not None:
+            raise ValueError("counts go with [B,R,4|5] rois")
+        N = box.shape[0]
+        if N == 0:
+            return torch.zeros((0,), dtype=torch.int32, device=dev)
+        R = min(N, MAX_ROWS)
+        G = (N + R - 1) // R
+        if G * R != N:                                          # the last group is filled with zero rows
+            box = torch.cat((box, torch.zeros((G * R - N, 4), dtype=box.dtype, device=dev)), 0)
+        box = box.reshape(G, R, 4)
+    else:
+        N = None
+        G, R = box.shape[0], box.shape[1]
+        if R > MAX_ROWS:
+            raise ValueError("at most %d rows per image (flat [N,4|5] input has no limit)" % MAX_ROWS)
+        if G == 0 or R == 0:
+            return torch.zeros((G, R), dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.full((G,), R, dtype=torch.int32, device=dev)
+    elif tuple(counts.shape) != (G,):
+        raise ValueError("counts must be int32 [B]")
+    lv = hip.prepare_proposals(box.contiguous(), counts, torch.ones((G,), dtype=torch.float32, device=dev), dedup_scale=0.0,
+                               k_min=k_min, k_max=k_max)["roi_levels"].clamp_(min=0)          # -1: a row past counts[b]
+    return lv if N is None else lv.reshape(-1)[:N]
+
+
 def map_rois_to_fpn_levels(rois, k_min, k_max, roi_canonical_scale=224, roi_canonical_level=4):
     """multilevel_rois.py:41-53 (canonical scale/level are the Detectron constants 224 / 4, fixed in the kernel)."""
     assert roi_canonical_scale == 224 and roi_canonical_level == 4
