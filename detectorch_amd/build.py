@@ -8,7 +8,8 @@ operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so), build_optim() for the 
 (csrc/optim/*.hip -> libdetectorch_optim_hip.so), build_rpn() for RPN training: anchor targets and the fused RPN losses
 (csrc/rpn_train/*.hip -> libdetectorch_rpn_hip.so), build_mask() for mask training: mask targets and the fused mask loss
 (csrc/mask_train/*.hip -> libdetectorch_mask_hip.so), build_eval() for scoring: COCO box AP and proposal recall
-(csrc/eval/*.hip -> libdetectorch_eval_hip.so).
+(csrc/eval/*.hip -> libdetectorch_eval_hip.so), build_segm() for scoring masks: RLE mask IoU and the match on it
+(csrc/segm_eval/*.hip -> libdetectorch_segm_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -79,9 +80,10 @@ def build(force=False, verbose=False):
 # ---- the side libraries, so that the inference library's ABI stays as it is: the training-side natives (include/detectorch_train_hip.h),
 # the head losses with their gradients (include/detectorch_loss_hip.h), the gradients of the region operators
 # (include/detectorch_grad_hip.h), the clipped SGD step (include/detectorch_optim_hip.h), RPN training
-# (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h) and scoring (include/detectorch_eval_hip.h).  sources()
-# globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip, csrc/optim/*.hip, csrc/rpn_train/*.hip, csrc/mask_train/*.hip
-# and csrc/eval/*.hip include the csrc/ headers by include path and are built with the same FLAGS, one
+# (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h), scoring (include/detectorch_eval_hip.h) and scoring
+# masks (include/detectorch_segm_hip.h).  sources()
+# globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip, csrc/optim/*.hip, csrc/rpn_train/*.hip, csrc/mask_train/*.hip,
+# csrc/eval/*.hip and csrc/segm_eval/*.hip include the csrc/ headers by include path and are built with the same FLAGS, one
 # library per directory.
 TRAIN_CSRC = os.path.join(CSRC, "train")
 TRAIN_LIB = os.path.join(LIBDIR, "libdetectorch_train_hip.so")
@@ -97,6 +99,8 @@ MASK_CSRC = os.path.join(CSRC, "mask_train")
 MASK_LIB = os.path.join(LIBDIR, "libdetectorch_mask_hip.so")
 EVAL_CSRC = os.path.join(CSRC, "eval")                       # scoring (include/detectorch_eval_hip.h): COCO box AP, proposal recall
 EVAL_LIB = os.path.join(LIBDIR, "libdetectorch_eval_hip.so")
+SEGM_CSRC = os.path.join(CSRC, "segm_eval")                  # scoring masks (include/detectorch_segm_hip.h): RLE mask IoU, segm matching
+SEGM_LIB = os.path.join(LIBDIR, "libdetectorch_segm_hip.so")
 
 
 def _side_sources(csrc):
@@ -166,6 +170,10 @@ def build_eval(force=False, verbose=False):
     return _build_side(EVAL_LIB, EVAL_CSRC, force, verbose)
 
 
+def build_segm(force=False, verbose=False):
+    return _build_side(SEGM_LIB, SEGM_CSRC, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
@@ -175,3 +183,4 @@ if __name__ == "__main__":
     print(build_rpn(force="--force" in sys.argv, verbose=True))
     print(build_mask(force="--force" in sys.argv, verbose=True))
     print(build_eval(force="--force" in sys.argv, verbose=True))
+    print(build_segm(force="--force" in sys.argv, verbose=True))

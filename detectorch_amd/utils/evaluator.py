@@ -1,7 +1,9 @@
-"""Box AP and proposal recall, scored on the device (hip_eval.py, include/detectorch_eval_hip.h).
+"""Box AP, mask AP and proposal recall, scored on the device (hip_eval.py, include/detectorch_eval_hip.h; hip_segm.py,
+include/detectorch_segm_hip.h).
 
-The reference scores its detections with pycocotools' COCOeval (lib/utils/json_dataset_evaluator.py:193-235) and its proposals
-with evaluate_box_proposals (:238-319).  Here both run as HIP kernels on the fixed-shape tensors of the batched path:
+The reference scores its detections with pycocotools' COCOeval (lib/utils/json_dataset_evaluator.py:193-235 for boxes, :40-64 and
+:116-124 for masks) and its proposals with evaluate_box_proposals (:238-319).  Here they run as HIP kernels on the fixed-shape
+tensors of the batched path:
 
     ev = BoxEvaluator(num_classes=81)
     for batch in loader:
@@ -9,8 +11,15 @@ with evaluate_box_proposals (:238-319).  Here both run as HIP kernels on the fix
         ev.update(dets, det_count, gt)             # gt: the dict the train steps take (+ optional gt_area); no host sync
     stats, per_class_ap = ev.summarize()           # COCO's twelve numbers, and the per-class AP the reference logs
 
-Out of scope: segm and keypoint evaluation (mask IoU over RLE), json files and category ids (result_utils.coco_bbox_results stays
-the way to an external scorer), reducing the records across ranks (gather the detections first, as dist.py does), non-finite scores.
+    mv = MaskEvaluator(num_classes=81)             # the same for iouType 'segm'
+    ...
+        rle = hip.mask_rle(hip.mask_paste(...), det_count, im_size)
+        mv.update(dets, det_count, rle, im_size, dict(gt, **pack_gt_masks(gt_masks, im_sizes, device)))
+    stats, per_class_ap = mv.summarize()
+
+Out of scope: keypoint evaluation (OKS), polygon -> RLE at image size (the loader's job: annToRLE where pycocotools exists;
+pack_gt_masks takes bitmaps and RLEs), json files and category ids (result_utils.coco_bbox_results / coco_segm_results stay the way
+to an external scorer), reducing the records across ranks (gather the detections first, as dist.py does), non-finite scores.
 """
 import warnings
 
@@ -18,6 +27,8 @@ import numpy as np
 import torch
 
 from .. import hip_eval
+from .. import hip_segm
+from . import result_utils
 
 # the reference's eight named area ranges (json_dataset_evaluator.py:247-264)
 PROPOSAL_AREAS = {'all': (0 ** 2, 1e5 ** 2), 'small': (0 ** 2, 32 ** 2), 'medium': (32 ** 2, 96 ** 2), 'large': (96 ** 2, 1e5 ** 2),
@@ -154,6 +165,52 @@ class BoxEvaluator:
         return res["stats"], dict(mean=mean, per_class=per_class)
 
 
+class MaskEvaluator(BoxEvaluator):
+    """Streaming COCO mask AP (COCOeval's iouType 'segm'): BoxEvaluator with the IoU of a pair taken between the masks
+    (dtc_segm_iou: maskApi.c's rleIou on the run lists) and the area of a detection being its mask's pixel count; the records, the
+    accumulation and the summary are the box protocol's.  update() makes no host sync and can be captured like BoxEvaluator's."""
+
+    def reset(self):
+        super().reset()
+        self._bad = []
+
+    def update(self, dets, det_count, det_rle, im_size, gt):
+        """dets f32 [N,max_out,6] and det_count i32 [N] on the device; det_rle: the dict hip.mask_rle returns (counts [N,max_out,
+        runs_stride], n_runs i32 [N,max_out]; the strings are not read); im_size [N,2] = (h, w) of the original images; gt: the dict
+        of BoxEvaluator.update (gt_boxes is not read) plus gt_runs [N,G,runs_stride'] / gt_n_runs i32 [N,G] (pack_gt_masks);
+        gt_area f32 [N,G] is the area of a gt when given (COCO's annotation area), else its mask's pixel count.  Every call must
+        have the same max_out.  -> the records of this call (hip_eval.match_outputs) plus iou, det_area, gt_mask_area and n_bad.
+        No host sync: a mask that did not fit hip.mask_rle's buffers (n_runs < 0) is scored as empty and reported by accumulate(),
+        as on_overflow says, like an image with det_count > max_out."""
+        if self._records and dets.shape[1] != self._records[0]["dt_rank"].shape[1]:
+            raise ValueError("update: max_out changed from %d to %d" % (self._records[0]["dt_rank"].shape[1], dets.shape[1]))
+        pairs = hip_segm.segm_iou(dets, det_count, det_rle["counts"], det_rle["n_runs"], im_size.to(torch.float32).contiguous(),
+                                  gt["gt_runs"], gt["gt_n_runs"], gt["gt_classes"], gt["gt_is_crowd"], gt["gt_counts"], self.num_classes)
+        rec = hip_segm.segm_match(dets, det_count, pairs["iou"], pairs["det_area"], gt["gt_classes"], gt["gt_is_crowd"], gt["gt_counts"],
+                                  gt.get("gt_area"), pairs["gt_mask_area"], self.num_classes, self._iou_thrs, self._area_rngs,
+                                  self.max_dets[-1], image_base=self.n_images)
+        rec.update(pairs)
+        self._records.append(rec)
+        self._counts.append((det_count.clone(), dets.shape[1]))
+        self._bad.append(pairs["n_bad"])
+        self.n_images += dets.shape[0]
+        self._result = None
+        return rec
+
+    def accumulate(self):
+        res = super().accumulate()
+        n_bad = torch.cat(self._bad).cpu().numpy()
+        bad = np.flatnonzero(n_bad > 0)
+        if len(bad):
+            msg = ("image %d: %d masks did not fit the RLE buffers (negative n_runs), %d in the run: encode them again with a larger "
+                   "runs_stride / crop capacity" % (bad[0], n_bad[bad[0]], int(n_bad.sum())))
+            if self.on_overflow == "raise":
+                self._result = None
+                raise RuntimeError(msg)
+            warnings.warn(msg + " -- scored as empty masks", RuntimeWarning)
+        return res
+
+
 def pack_gt(roidb, device, G=None):
     """roidb-style dicts (boxes, gt_classes, is_crowd, seg_areas; rows with gt_classes == 0 are proposals and left out) -> the gt dict
     of BoxEvaluator.update on `device`"""
@@ -192,6 +249,102 @@ def evaluate_boxes(all_boxes, roidb, device="cuda", batch=256, **evaluator_args)
                 at += len(d)
         ev.update(torch.from_numpy(dets).to(ev.device), torch.tensor(count[i0:i1], dtype=torch.int32, device=ev.device),
                   pack_gt(roidb[i0:i1], ev.device, G))
+    ev.accumulate()
+    return ev
+
+
+def _gt_runs(m, h, w, where):
+    """one gt mask in any accepted form -> its run lengths as int64, or None"""
+    if m is None:
+        return None
+    if isinstance(m, dict):
+        if [int(v) for v in m['size']] != [h, w]:
+            raise ValueError("%s: an RLE of size %s in an image of size %s" % (where, list(m['size']), [h, w]))
+        c = m['counts']
+        runs = np.asarray(result_utils.rle_string_to_counts(c) if isinstance(c, (str, bytes)) else c, np.int64).reshape(-1)
+    else:
+        m = np.asarray(m)
+        if m.shape != (h, w):
+            raise ValueError("%s: a bitmap of shape %s in an image of size %s" % (where, m.shape, (h, w)))
+        runs = np.asarray(result_utils.rle_counts(m), np.int64)
+    if len(runs) and (runs.min() < 0 or runs.max() > 0xffffffff):
+        raise ValueError("%s: run lengths must be in 0 .. 2^32 - 1" % where)
+    return runs
+
+
+def pack_gt_masks(masks_per_image, im_sizes, device, G=None, runs_stride=None):
+    """masks_per_image[i][j]: the mask of gt row j of image i (the rows of pack_gt, in its order) as a binary [h, w] array, an
+    uncompressed RLE (dict(size=[h, w], counts=list)), a compressed RLE (counts as str / bytes) or None (no segmentation: an empty
+    mask); im_sizes [N, 2] = (h, w).  -> dict(gt_runs int32 [N, G, runs_stride] holding the uint32 run lengths, gt_n_runs int32
+    [N, G]) on `device`, to be merged into the gt dict of MaskEvaluator.update.  Polygons are not taken: convert them at image size
+    first (annToRLE)."""
+    im_sizes = np.asarray(im_sizes).reshape(len(masks_per_image), 2)
+    runs = [[_gt_runs(m, int(im_sizes[i, 0]), int(im_sizes[i, 1]), "image %d gt %d" % (i, j)) for j, m in enumerate(ms)]
+            for i, ms in enumerate(masks_per_image)]
+    N = len(runs)
+    need_G, need_stride = max([1] + [len(r) for r in runs]), max([1] + [len(x) for r in runs for x in r if x is not None])
+    G, runs_stride = need_G if G is None else int(G), need_stride if runs_stride is None else int(runs_stride)
+    if need_G > G or need_stride > runs_stride:
+        raise ValueError("pack_gt_masks: %d gt of up to %d runs do not fit G = %d, runs_stride = %d" % (need_G, need_stride, G, runs_stride))
+    out, n_runs = np.zeros((N, G, runs_stride), np.uint32), np.zeros((N, G), np.int32)
+    for i, r in enumerate(runs):
+        for j, x in enumerate(r):
+            if x is not None:
+                out[i, j, :len(x)], n_runs[i, j] = x, len(x)
+    return dict(gt_runs=torch.from_numpy(out.view(np.int32)).to(device), gt_n_runs=torch.from_numpy(n_runs).to(device))
+
+
+def evaluate_masks(all_boxes, all_segms, roidb, gt_masks, device="cuda", batch=64, **evaluator_args):
+    """The reference-shaped convenience (json_dataset_evaluator.py:evaluate_masks without the json files): all_boxes[cls][image] =
+    [k,5] and all_segms[cls][image] = k RLE dicts (size, compressed counts) as result_utils.assemble_results leaves them; roidb: a
+    list of dicts (boxes, gt_classes, is_crowd, seg_areas as for evaluate_boxes; height and width, or the sizes are read off the RLEs); gt_masks[image][j]: the
+    mask of the j-th row with gt_classes > 0, in any form pack_gt_masks takes.  -> the MaskEvaluator after accumulate().
+    Out of scope: polygon -> RLE at image size (the loader's job: annToRLE where pycocotools exists), json files, category ids,
+    keypoints."""
+    num_classes, N = len(all_boxes), len(roidb)
+    per_image, sizes = [], np.zeros((N, 2), np.int64)
+    for i in range(N):
+        rows = []
+        for j in range(1, num_classes):
+            b = np.asarray(all_boxes[j][i], np.float32).reshape(-1, 5)
+            if len(b) != len(all_segms[j][i]):
+                raise ValueError("evaluate_masks: image %d class %d: %d boxes and %d masks" % (i, j, len(b), len(all_segms[j][i])))
+            rows += [(j, b[k], all_segms[j][i][k]) for k in range(len(b))]
+        per_image.append(rows)
+        e = roidb[i]
+        known = [s['size'] for _, _, s in rows] + [m['size'] for m in gt_masks[i] if isinstance(m, dict)] + \
+                [np.asarray(m).shape for m in gt_masks[i] if m is not None and not isinstance(m, dict)]
+        if 'height' in e and 'width' in e:
+            sizes[i] = (e['height'], e['width'])
+        elif known:
+            sizes[i] = known[0]
+        for _, _, s in rows:
+            if [int(v) for v in s['size']] != sizes[i].tolist():
+                raise ValueError("evaluate_masks: image %d: a mask of size %s in an image of size %s" % (i, list(s['size']), sizes[i].tolist()))
+    det_runs = [[np.asarray(result_utils.rle_string_to_counts(s['counts']) if isinstance(s['counts'], (str, bytes)) else s['counts'],
+                            np.int64) for _, _, s in rows] for rows in per_image]
+    max_out, stride = max([1] + [len(r) for r in per_image]), max([1] + [len(x) for r in det_runs for x in r])
+    if max_out > hip_eval.MAX_OUT:
+        raise ValueError("evaluate_masks: an image has %d detections, at most %d" % (max_out, hip_eval.MAX_OUT))
+    n_gt = [int((np.asarray(e['gt_classes']) > 0).sum()) for e in roidb]
+    G = max([1] + n_gt)
+    gt_stride = None
+    ev = MaskEvaluator(num_classes=num_classes, device=device, **evaluator_args)
+    dev = ev.device
+    for i0 in range(0, N, batch):
+        i1 = min(N, i0 + batch)
+        dets, counts = np.zeros((i1 - i0, max_out, 6), np.float32), np.zeros((i1 - i0, max_out, stride), np.uint32)
+        n_runs = np.zeros((i1 - i0, max_out), np.int32)
+        for i in range(i0, i1):
+            for at, (j, b, _) in enumerate(per_image[i]):
+                dets[i - i0, at, :5], dets[i - i0, at, 5] = b, j
+                x = det_runs[i][at]
+                counts[i - i0, at, :len(x)], n_runs[i - i0, at] = x, len(x)
+        gt = pack_gt(roidb[i0:i1], dev, G)                      # gt_boxes is not read
+        gt.update(pack_gt_masks(gt_masks[i0:i1], sizes[i0:i1], dev, G, gt_stride))
+        t = lambda a: torch.from_numpy(a).to(dev)
+        ev.update(t(dets), torch.tensor([len(r) for r in per_image[i0:i1]], dtype=torch.int32, device=dev),
+                  dict(counts=t(counts.view(np.int32)), n_runs=t(n_runs)), t(sizes[i0:i1].astype(np.float32)), gt)
     ev.accumulate()
     return ev
 

@@ -153,15 +153,42 @@ def _rle_counts_to_string(cnts):
     return "".join(out)
 
 
-def rle_encode(mask):
-    """mask [h,w] uint8 -> {'size': [h,w], 'counts': str}: column-major run lengths starting with a run of zeros."""
-    h, w = mask.shape
+def rle_string_to_counts(s):
+    """The inverse of _rle_counts_to_string (pycocotools rleFrString): a compressed "counts" string (str or bytes) -> the run
+    lengths as a list of ints."""
+    if isinstance(s, str):
+        s = s.encode('ascii')
+    cnts, p = [], 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            c = s[p] - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x)
+    return cnts
+
+
+def rle_counts(mask):
+    """mask [h,w] of 0 / 1 -> COCO's uncompressed run lengths as a list: column-major, starting with a run of zeros."""
     flat = np.asarray(mask, np.uint8).reshape(-1, order='F')
     change = np.flatnonzero(np.diff(flat)) + 1
     runs = np.diff(np.concatenate([[0], change, [flat.size]]))
     if flat.size and flat[0] == 1:
         runs = np.concatenate([[0], runs])
-    return {'size': [int(h), int(w)], 'counts': _rle_counts_to_string(runs.tolist())}
+    return runs.tolist()
+
+
+def rle_encode(mask):
+    """mask [h,w] uint8 -> {'size': [h,w], 'counts': str}: column-major run lengths starting with a run of zeros."""
+    h, w = mask.shape
+    return {'size': [int(h), int(w)], 'counts': _rle_counts_to_string(rle_counts(mask))}
 
 
 def segm_results(cls_boxes, masks, ref_boxes, im_h, im_w, num_classes=81, M=14, cls_specific_mask=True,
