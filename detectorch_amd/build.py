@@ -9,7 +9,8 @@ operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so), build_optim() for the 
 (csrc/rpn_train/*.hip -> libdetectorch_rpn_hip.so), build_mask() for mask training: mask targets and the fused mask loss
 (csrc/mask_train/*.hip -> libdetectorch_mask_hip.so), build_eval() for scoring: COCO box AP and proposal recall
 (csrc/eval/*.hip -> libdetectorch_eval_hip.so), build_segm() for scoring masks: RLE mask IoU and the match on it
-(csrc/segm_eval/*.hip -> libdetectorch_segm_hip.so).
+(csrc/segm_eval/*.hip -> libdetectorch_segm_hip.so), build_poly() for ground-truth polygons at image size to run lists
+(csrc/poly_rle/*.hip -> libdetectorch_poly_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -80,11 +81,11 @@ def build(force=False, verbose=False):
 # ---- the side libraries, so that the inference library's ABI stays as it is: the training-side natives (include/detectorch_train_hip.h),
 # the head losses with their gradients (include/detectorch_loss_hip.h), the gradients of the region operators
 # (include/detectorch_grad_hip.h), the clipped SGD step (include/detectorch_optim_hip.h), RPN training
-# (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h), scoring (include/detectorch_eval_hip.h) and scoring
-# masks (include/detectorch_segm_hip.h).  sources()
+# (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h), scoring (include/detectorch_eval_hip.h), scoring
+# masks (include/detectorch_segm_hip.h) and polygons to run lists (include/detectorch_poly_hip.h).  sources()
 # globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip, csrc/optim/*.hip, csrc/rpn_train/*.hip, csrc/mask_train/*.hip,
-# csrc/eval/*.hip and csrc/segm_eval/*.hip include the csrc/ headers by include path and are built with the same FLAGS, one
-# library per directory.
+# csrc/eval/*.hip, csrc/segm_eval/*.hip and csrc/poly_rle/*.hip include the csrc/ headers by include path and are built with the same
+# FLAGS, one library per directory.
 TRAIN_CSRC = os.path.join(CSRC, "train")
 TRAIN_LIB = os.path.join(LIBDIR, "libdetectorch_train_hip.so")
 LOSS_CSRC = os.path.join(CSRC, "loss")
@@ -101,6 +102,8 @@ EVAL_CSRC = os.path.join(CSRC, "eval")                       # scoring (include/
 EVAL_LIB = os.path.join(LIBDIR, "libdetectorch_eval_hip.so")
 SEGM_CSRC = os.path.join(CSRC, "segm_eval")                  # scoring masks (include/detectorch_segm_hip.h): RLE mask IoU, segm matching
 SEGM_LIB = os.path.join(LIBDIR, "libdetectorch_segm_hip.so")
+POLY_CSRC = os.path.join(CSRC, "poly_rle")                   # gt polygons at image size to run lists (include/detectorch_poly_hip.h): annToRLE
+POLY_LIB = os.path.join(LIBDIR, "libdetectorch_poly_hip.so")
 
 
 def _side_sources(csrc):
@@ -174,6 +177,10 @@ def build_segm(force=False, verbose=False):
     return _build_side(SEGM_LIB, SEGM_CSRC, force, verbose)
 
 
+def build_poly(force=False, verbose=False):
+    return _build_side(POLY_LIB, POLY_CSRC, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
@@ -184,3 +191,4 @@ if __name__ == "__main__":
     print(build_mask(force="--force" in sys.argv, verbose=True))
     print(build_eval(force="--force" in sys.argv, verbose=True))
     print(build_segm(force="--force" in sys.argv, verbose=True))
+    print(build_poly(force="--force" in sys.argv, verbose=True))

@@ -17,8 +17,9 @@ tensors of the batched path:
         mv.update(dets, det_count, rle, im_size, dict(gt, **pack_gt_masks(gt_masks, im_sizes, device)))
     stats, per_class_ap = mv.summarize()
 
-Out of scope: keypoint evaluation (OKS), polygon -> RLE at image size (the loader's job: annToRLE where pycocotools exists;
-pack_gt_masks takes bitmaps and RLEs), json files and category ids (result_utils.coco_bbox_results / coco_segm_results stay the way
+Ground-truth polygons go through utils/segms.py:pack_gt_segms (polygon -> RLE at image size on the device, hip_poly.py;
+pack_gt_masks itself takes bitmaps and RLEs); evaluate_masks takes either.
+Out of scope: keypoint evaluation (OKS), json files and category ids (result_utils.coco_bbox_results / coco_segm_results stay the way
 to an external scorer), reducing the records across ranks (gather the detections first, as dist.py does), non-finite scores.
 """
 import warnings
@@ -276,8 +277,8 @@ def pack_gt_masks(masks_per_image, im_sizes, device, G=None, runs_stride=None):
     """masks_per_image[i][j]: the mask of gt row j of image i (the rows of pack_gt, in its order) as a binary [h, w] array, an
     uncompressed RLE (dict(size=[h, w], counts=list)), a compressed RLE (counts as str / bytes) or None (no segmentation: an empty
     mask); im_sizes [N, 2] = (h, w).  -> dict(gt_runs int32 [N, G, runs_stride] holding the uint32 run lengths, gt_n_runs int32
-    [N, G]) on `device`, to be merged into the gt dict of MaskEvaluator.update.  Polygons are not taken: convert them at image size
-    first (annToRLE)."""
+    [N, G]) on `device`, to be merged into the gt dict of MaskEvaluator.update.  Polygons are not taken here:
+    utils/segms.py:pack_gt_segms converts them at image size on the device (annToRLE) and hands every other form to this function."""
     im_sizes = np.asarray(im_sizes).reshape(len(masks_per_image), 2)
     runs = [[_gt_runs(m, int(im_sizes[i, 0]), int(im_sizes[i, 1]), "image %d gt %d" % (i, j)) for j, m in enumerate(ms)]
             for i, ms in enumerate(masks_per_image)]
@@ -298,9 +299,10 @@ def evaluate_masks(all_boxes, all_segms, roidb, gt_masks, device="cuda", batch=6
     """The reference-shaped convenience (json_dataset_evaluator.py:evaluate_masks without the json files): all_boxes[cls][image] =
     [k,5] and all_segms[cls][image] = k RLE dicts (size, compressed counts) as result_utils.assemble_results leaves them; roidb: a
     list of dicts (boxes, gt_classes, is_crowd, seg_areas as for evaluate_boxes; height and width, or the sizes are read off the RLEs); gt_masks[image][j]: the
-    mask of the j-th row with gt_classes > 0, in any form pack_gt_masks takes.  -> the MaskEvaluator after accumulate().
-    Out of scope: polygon -> RLE at image size (the loader's job: annToRLE where pycocotools exists), json files, category ids,
-    keypoints."""
+    mask of the j-th row with gt_classes > 0, in any form pack_gt_masks takes, or a list of COCO polygons (the annotation's
+    `segmentation` as it is: converted at image size on the device, utils/segms.py:pack_gt_segms; the roidb entry must then carry
+    height and width unless another mask of the image tells them).  -> the MaskEvaluator after accumulate().
+    Out of scope: json files, category ids, keypoints."""
     num_classes, N = len(all_boxes), len(roidb)
     per_image, sizes = [], np.zeros((N, 2), np.int64)
     for i in range(N):
@@ -313,11 +315,13 @@ def evaluate_masks(all_boxes, all_segms, roidb, gt_masks, device="cuda", batch=6
         per_image.append(rows)
         e = roidb[i]
         known = [s['size'] for _, _, s in rows] + [m['size'] for m in gt_masks[i] if isinstance(m, dict)] + \
-                [np.asarray(m).shape for m in gt_masks[i] if m is not None and not isinstance(m, dict)]
+                [np.asarray(m).shape for m in gt_masks[i] if m is not None and not isinstance(m, (dict, list, tuple))]
         if 'height' in e and 'width' in e:
             sizes[i] = (e['height'], e['width'])
         elif known:
             sizes[i] = known[0]
+        elif any(isinstance(m, (list, tuple)) for m in gt_masks[i]):
+            raise ValueError("evaluate_masks: image %d has polygons and nothing tells its size: give height and width in the roidb" % i)
         for _, _, s in rows:
             if [int(v) for v in s['size']] != sizes[i].tolist():
                 raise ValueError("evaluate_masks: image %d: a mask of size %s in an image of size %s" % (i, list(s['size']), sizes[i].tolist()))
@@ -341,7 +345,12 @@ def evaluate_masks(all_boxes, all_segms, roidb, gt_masks, device="cuda", batch=6
                 x = det_runs[i][at]
                 counts[i - i0, at, :len(x)], n_runs[i - i0, at] = x, len(x)
         gt = pack_gt(roidb[i0:i1], dev, G)                      # gt_boxes is not read
-        gt.update(pack_gt_masks(gt_masks[i0:i1], sizes[i0:i1], dev, G, gt_stride))
+        if any(isinstance(m, (list, tuple)) for ms in gt_masks[i0:i1] for m in ms):
+            from . import segms                                # (segms imports this module)
+            packed = segms.pack_gt_segms(gt_masks[i0:i1], sizes[i0:i1], dev, G, gt_stride)
+            gt.update(gt_runs=packed["gt_runs"], gt_n_runs=packed["gt_n_runs"])
+        else:
+            gt.update(pack_gt_masks(gt_masks[i0:i1], sizes[i0:i1], dev, G, gt_stride))
         t = lambda a: torch.from_numpy(a).to(dev)
         ev.update(t(dets), torch.tensor([len(r) for r in per_image[i0:i1]], dtype=torch.int32, device=dev),
                   dict(counts=t(counts.view(np.int32)), n_runs=t(n_runs)), t(sizes[i0:i1].astype(np.float32)), gt)

@@ -1,0 +1,209 @@
+"""The checker of the polygon conversion (test support, not a test module): the contract of include/detectorch_poly_hip.h restated in
+numpy, one gt row at a time -- the RASTERISATION RULE's trace written out point by point for a height h and a width w (one numpy
+expression per edge: the same float64 operations in the same order as the header's text), the parity per polygon on a bitmap, the OR
+per instance, and a run-length coding of the column-major bitmap that does not use result_utils.
+
+    trace_positions   the events of one polygon: the toggled column-major positions (those < h w)
+    poly_bitmap       one polygon -> flat column-major bool [h w]
+    row               one gt row of a case -> None (takes part in nothing) or (flat bitmap, events)
+    runs_of           flat bitmap -> COCO's uncompressed run lengths
+    run               a whole case -> what dtc_poly_rle must write: n_runs, runs (lists), area, need
+    even_odd_hw       the independent check of tests/mask_train_ref.even_odd, for h x w
+
+COCO's own code (pycocotools) is not available: the rule is restated from the published algorithm (common/maskApi.c:rleFrPoly,
+rleMerge) and parity with pycocotools itself is unpinned (tests/README_poly_rle.md).
+"""
+import numpy as np
+
+MAX_PIXELS = 1 << 30
+COORD_LIMIT = 2.0 ** 26
+MAX_EVENTS = 8192
+
+
+def side(v):
+    """one side of im_size: truncated; below 1, NaN: 0; above 2^30: 2^30"""
+    v = np.float32(v)
+    if not v >= 1:
+        return 0
+    return MAX_PIXELS if v >= np.float32(MAX_PIXELS) else int(v)
+
+
+def pixels(im_size):
+    return min(side(im_size[0]) * side(im_size[1]), MAX_PIXELS)
+
+
+def trace_positions(xy, h, w):
+    """xy [n, 2] float64 -> int64 array of the toggled positions, in trace order"""
+    xy = np.asarray(xy, np.float64)
+    X = (5.0 * xy[:, 0] + 0.5).astype(np.int64)                # astype: C's (int), toward zero
+    Y = (5.0 * xy[:, 1] + 0.5).astype(np.int64)
+    n, out = len(X), []
+    hw = min(h * w, MAX_PIXELS)
+    for k in range(n):
+        xs, ys, xe, ye = int(X[k]), int(Y[k]), int(X[(k + 1) % n]), int(Y[(k + 1) % n])
+        dx, dy = abs(xe - xs), abs(ye - ys)
+        if dx == 0 and dy == 0:
+            continue
+        if dx >= dy:
+            if xs > xe:
+                xs, ys, xe, ye = xe, ye, xs, ys
+            s = float(ye - ys) / dx
+            t = np.arange(dx + 1, dtype=np.float64)
+            u = xs + np.arange(dx + 1, dtype=np.int64)
+            v = (ys + s * t + 0.5).astype(np.int64)
+        else:
+            if ys > ye:
+                xs, ys, xe, ye = xe, ye, xs, ys
+            s = float(xe - xs) / dy
+            t = np.arange(dy + 1, dtype=np.float64)
+            u = (xs + s * t + 0.5).astype(np.int64)
+            v = ys + np.arange(dy + 1, dtype=np.int64)
+        us, vs = np.minimum(u[:-1], u[1:]), np.minimum(v[:-1], v[1:])
+        i = (us - 2) // 5
+        ev = (u[:-1] != u[1:]) & ((us - 2) % 5 == 0) & (i >= 0) & (i <= w - 1)
+        i, vs = i[ev], vs[ev]
+        j = np.ceil(np.minimum(np.maximum((vs + 0.5) / 5.0 - 0.5, 0.0), float(h))).astype(np.int64)
+        pos = i * h + j
+        out.append(pos[pos < hw])
+    return np.concatenate(out) if out else np.zeros(0, np.int64)
+
+
+def poly_bitmap(xy, h, w):
+    """(flat column-major bool [h w], the number of events)"""
+    pos = trace_positions(xy, h, w)
+    tog = np.zeros(h * w, np.int64)
+    np.add.at(tog, pos, 1)
+    return (np.cumsum(tog) % 2).astype(bool), len(pos)
+
+
+def valid_polys(case, n, g):
+    """the valid polygons of gt row g of image n as [k, 2] float64 arrays; None: the row's own range is malformed"""
+    ptr, gptr, xy = case["poly_ptr"][n], case["gt_poly_ptr"][n], case["poly_xy"][n]
+    NP, PTS = len(ptr) - 1, len(xy)
+    q0, q1 = int(gptr[g]), int(gptr[g + 1])
+    if not (q0 >= 0 and q1 <= NP and q0 <= q1):
+        return None
+    out = []
+    for q in range(q0, q1):
+        ps, pe = int(ptr[q]), int(ptr[q + 1])
+        if ps >= 0 and pe <= PTS and ps <= pe - 3 and np.isfinite(xy[ps:pe]).all():
+            out.append(xy[ps:pe])
+    return out
+
+
+def row(case, n, g):
+    """None: the row takes part in nothing; else (flat bitmap, events)"""
+    G = case["gt_poly_ptr"].shape[1] - 1
+    h, w = side(case["im_size"][n, 0]), side(case["im_size"][n, 1])
+    if g >= min(max(int(case["gt_counts"][n]), 0), G) or h * w == 0 or case["poly_ptr"].shape[1] < 2 or case["poly_xy"].shape[1] == 0:
+        return None
+    polys = valid_polys(case, n, g)
+    if not polys:
+        return None
+    acc, events = np.zeros(h * w, bool), 0
+    for p in polys:
+        if not (np.abs(p) < COORD_LIMIT).all():
+            continue
+        m, e = poly_bitmap(p, h, w)
+        acc |= m
+        events += e
+    return acc, events
+
+
+def runs_of(flat):
+    """flat bool [h w] -> run lengths: zeros first, alternating, summing to h w"""
+    runs, cur, length = [], False, 0
+    for v in flat.tolist():
+        if v == cur:
+            length += 1
+        else:
+            runs.append(length)
+            cur, length = v, 1
+    runs.append(length)
+    return runs
+
+
+def run(case, runs_stride, events_stride):
+    """-> dict(n_runs int32 [N,G], runs [N][G] lists (None where n_runs < 1), area int32 [N,G], need int32 [N,G,2], bitmaps [N][G] [h,w]
+    bool arrays or None)"""
+    N, G = case["gt_poly_ptr"].shape[0], case["gt_poly_ptr"].shape[1] - 1
+    n_runs, area, need = np.zeros((N, G), np.int32), np.zeros((N, G), np.int32), np.zeros((N, G, 2), np.int32)
+    runs, bitmaps = [[None] * G for _ in range(N)], [[None] * G for _ in range(N)]
+    for n in range(N):
+        h, w = side(case["im_size"][n, 0]), side(case["im_size"][n, 1])
+        for g in range(G):
+            r = row(case, n, g)
+            if r is None:
+                continue
+            flat, events = r
+            bitmaps[n][g] = flat.reshape(w, h).T.copy()
+            if events > events_stride:
+                n_runs[n, g], need[n, g] = -1, (events, -1)
+                continue
+            rl = runs_of(flat)
+            need[n, g] = (events, len(rl))
+            if len(rl) > runs_stride:
+                n_runs[n, g] = -1
+                continue
+            n_runs[n, g], area[n, g], runs[n][g] = len(rl), int(flat.sum()), rl
+    return dict(n_runs=n_runs, runs=runs, area=area, need=need, bitmaps=bitmaps)
+
+
+def pack(polys_per_image, G=None, PTS=None, NP=None, dtype=np.float64):
+    """per image, per gt row a list of [k, 2] arrays -> dict(poly_xy [N,PTS,2], poly_ptr [N,NP+1], gt_poly_ptr [N,G+1]); the layout
+    of detectorch_amd.utils.segms.pack_polygons64, written on its own"""
+    per = []
+    for im in polys_per_image:
+        xy, ptr, gptr = [], [0], [0]
+        for polys in im:
+            for p in polys:
+                p = np.asarray(p, dtype).reshape(-1, 2)
+                xy.append(p)
+                ptr.append(ptr[-1] + len(p))
+            gptr.append(len(ptr) - 1)
+        per.append((np.concatenate(xy) if xy else np.zeros((0, 2), dtype), ptr, gptr))
+    N = len(per)
+    G = max([1] + [len(g) - 1 for _, _, g in per]) if G is None else G
+    PTS = max([1] + [len(x) for x, _, _ in per]) if PTS is None else PTS
+    NP = max([1] + [len(p) - 1 for _, p, _ in per]) if NP is None else NP
+    poly_xy, poly_ptr, gt_poly_ptr = np.zeros((N, PTS, 2), dtype), np.zeros((N, NP + 1), np.int32), np.zeros((N, G + 1), np.int32)
+    for b, (xy, ptr, gptr) in enumerate(per):
+        poly_xy[b, :len(xy)] = xy
+        poly_ptr[b, :len(ptr)], poly_ptr[b, len(ptr):] = ptr, ptr[-1]
+        gt_poly_ptr[b, :len(gptr)], gt_poly_ptr[b, len(gptr):] = gptr, gptr[-1]
+    return dict(poly_xy=poly_xy, poly_ptr=poly_ptr, gt_poly_ptr=gt_poly_ptr)
+
+
+def make_case(polys_per_image, im_sizes, gt_counts=None, **pack_args):
+    c = pack(polys_per_image, **pack_args)
+    c["im_size"] = np.asarray(im_sizes, np.float32).reshape(len(polys_per_image), 2)
+    c["gt_counts"] = np.asarray([len(im) for im in polys_per_image] if gt_counts is None else gt_counts, np.int32)
+    return c
+
+
+def instance_bitmap(polygons, h, w):
+    """a list of COCO polygons [x0, y0, x1, y1, ...] -> bool [h, w]: the union, by the restatement"""
+    acc = np.zeros(h * w, bool)
+    for p in polygons:
+        acc |= poly_bitmap(np.asarray(p, np.float64).reshape(-1, 2), h, w)[0]
+    return acc.reshape(w, h).T.copy()
+
+
+def even_odd_hw(xy, h, w):
+    """tests/mask_train_ref.even_odd for an h x w image: the even-odd rule at the pixel centres (x + 0.5, y + 0.5), written without the
+    trace -> uint8 [h, w]"""
+    p = np.asarray(xy, np.float64)
+    q = np.roll(p, -1, axis=0)
+    cx, cy = (np.arange(w) + 0.5)[None, :, None], (np.arange(h) + 0.5)[:, None, None]
+    x0, y0, x1, y1 = p[:, 0], p[:, 1], q[:, 0], q[:, 1]
+    straddle = (y0 <= cy) != (y1 <= cy)
+    with np.errstate(all="ignore"):
+        xi = x0 + (cy - y0) * (x1 - x0) / (y1 - y0)
+    return ((straddle & (xi > cx)).sum(axis=2) % 2).astype(np.uint8)
+
+
+def star(cx, cy, r_out, r_in, n):
+    """a star polygon of n vertices (n even) around (cx, cy), float64 [n, 2]"""
+    a = np.linspace(0, 2 * np.pi, n, endpoint=False)
+    rad = np.where(np.arange(n) % 2 == 0, r_out, r_in)
+    return np.stack([cx + rad * np.cos(a), cy + rad * np.sin(a)], 1)
