@@ -2,15 +2,17 @@
 
     prep_im_for_blob   blob.py:62-87   mean-subtract + cv2.resize(fx=fy=im_scale, INTER_LINEAR), numpy in / numpy out
     im_list_to_blob    blob.py:27-59   zero-pad to the batch max (rounded up to the FPN stride) + HWC -> NCHW
-    images_to_blob     (extension)     both in ONE launch, device in / device out: what a serving loop should call
+    images_to_blob     (extension)     both in ONE launch, device in / device out: what a serving loop should call; with
+                                       flipped=, images mirrored left to right first (coco_dataset.py:51-53) in the same launch
 
-The arithmetic runs in detectorch_amd/csrc/prep_image.hip (dtc_prep_images); there is no CPU fallback.  cv2 is not needed
+The arithmetic runs in detectorch_amd/csrc/prep_image.hip (dtc_prep_images) and, for a batch with mirrored images, in
+csrc/flip/flip_prep.hip (dtc_flip_prep_images) -- one per-pixel text, csrc/prep_pixel.h; there is no CPU fallback.  cv2 is not needed
 (and not installed here): the resize rule is OpenCV's documented INTER_LINEAR, "parity unpinned" (DESIGN.md).
 """
 import numpy as np
 import torch
 
-from .. import hip
+from .. import hip, hip_flip
 
 PIXEL_MEANS = [122.7717, 115.9465, 102.9801]     # blob.py:62 (BGR)
 
@@ -21,9 +23,13 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def images_to_blob(images, pixel_means=PIXEL_MEANS, target_size=800, max_size=1333, fpn_on=False, fpn_coarsest_stride=32):
+def images_to_blob(images, pixel_means=PIXEL_MEANS, target_size=800, max_size=1333, fpn_on=False, fpn_coarsest_stride=32,
+                   flipped=None):
     """list of HWC BGR images (CUDA tensors or numpy arrays, uint8 / float32) -> (blob float32 CUDA [B,3,Hb,Wb],
-    im_scales list).  Equivalent to im_list_to_blob([prep_im_for_blob(im)[0][0] for im in images], fpn_on)."""
+    im_scales list).  Equivalent to im_list_to_blob([prep_im_for_blob(im)[0][0] for im in images], fpn_on).
+    flipped: None, or one host flag per image: image b is mirrored left to right first (image[:, ::-1, :], the reference's flipped
+    roidb entry) -- bit-equal to passing the mirrored image, at no extra pass over the pixels.  None or all false: exactly the call
+    without it."""
     dev = _dev()
     ts = []
     for im in images:
@@ -31,7 +37,13 @@ def images_to_blob(images, pixel_means=PIXEL_MEANS, target_size=800, max_size=13
         if t.dtype not in (torch.uint8, torch.float32):
             t = t.to(torch.float32)
         ts.append(t.to(dev))
-    blob, scales, _ = hip.prep_images(ts, pixel_means, target_size, max_size, fpn_coarsest_stride if fpn_on else 1)
+    pad_stride = fpn_coarsest_stride if fpn_on else 1
+    if flipped is not None and len(flipped) != len(ts):
+        raise ValueError("images_to_blob: %d flags for %d images" % (len(flipped), len(ts)))
+    if flipped is None or not any(bool(f) for f in flipped):
+        blob, scales, _ = hip.prep_images(ts, pixel_means, target_size, max_size, pad_stride)
+    else:
+        blob, scales, _ = hip_flip.prep_images(ts, [bool(f) for f in flipped], pixel_means, target_size, max_size, pad_stride)
     return blob, scales
 
 

@@ -8,13 +8,14 @@ same names and numpy-in / numpy-out conventions, computed by the HIP kernels (de
     box_voting       boxes.py:280-329   -> dtc_box_voting (+ host statistics for the non-'ID' scoring methods)
     clip_tiled_boxes boxes.py:150-165
     expand_boxes     boxes.py:245-261 ; boxes_area boxes.py:75-81  (trivial host numpy, identical arithmetic)
+    flip_boxes       boxes.py:264-269   -> dtc_flip_boxes     (the side library of hip_flip.py)
 
 There is no CPU fallback for the kernels: without the GPU library these raise.
 """
 import numpy as np
 import torch
 
-from .. import hip
+from .. import hip, hip_flip
 
 cfg_BBOX_XFORM_CLIP = 4.135166556742356   # boxes.py:73
 
@@ -97,6 +98,18 @@ def expand_boxes(boxes, scale):
     boxes_exp[:, 1] = y_c - h_half
     boxes_exp[:, 3] = y_c + h_half
     return boxes_exp
+
+
+def flip_boxes(boxes, im_width):
+    """Flip boxes horizontally (boxes.py:264-269): boxes [n, 4k] -> float32 [n, 4k] with x1' = im_width - x2 - 1 and x2' = im_width -
+    x1 - 1 in every group of four columns, in float32 as numpy evaluates it for float32 boxes."""
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    assert b.ndim == 2 and b.shape[1] % 4 == 0 and b.shape[1] > 0
+    if b.shape[0] == 0:
+        return b.copy()
+    dev = _dev()
+    out = hip_flip.flip_boxes(torch.from_numpy(b).to(dev).unsqueeze(0), torch.tensor([int(im_width)], dtype=torch.int32, device=dev), [1])
+    return out[0].cpu().numpy()
 
 
 def bbox_overlaps(boxes, query_boxes):

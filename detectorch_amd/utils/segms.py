@@ -9,13 +9,16 @@ itself is unpinned (tests/README_poly_rle.md).
     gt.update(pack_gt_segms(segms_per_image, im_sizes, device))      # polygons, crowd RLEs, bitmaps, None -- as the file has them
     mask_evaluator.update(dets, det_count, rle, im_size, gt)
 
-There is no CPU fallback: a polygon needs a GPU.  polys_to_mask_wrt_box is csrc/mask_train's (mask_rcnn_targets.py); flip_segms and
-the rle_mask_* functions of the reference are out of scope.
+flip_segms is the reference's (segms.py:35-61): polygon lists are mirrored in Python doubles -- a list is loader data, and it is the
+arithmetic of dtc_flip_polygons --, RLE dicts go through dtc_flip_rle (hip_flip.py), which mirrors the run list without a bitmap.
+
+There is no CPU fallback: a polygon to convert, or an RLE to flip, needs a GPU.  polys_to_mask_wrt_box is csrc/mask_train's
+(mask_rcnn_targets.py); the rle_mask_* functions of the reference are out of scope.
 """
 import numpy as np
 import torch
 
-from .. import hip_poly
+from .. import hip_flip, hip_poly
 from . import result_utils
 from .evaluator import pack_gt_masks
 from .mask_rcnn_targets import pack_polygons
@@ -168,3 +171,49 @@ def polys_to_boxes(polys):
         ys = np.concatenate([np.asarray(p, np.float64)[1::2] for p in poly])
         boxes[i] = [xs.min(), ys.min(), xs.max(), ys.max()]
     return boxes
+
+
+def _flip_poly(poly, width):
+    """segms.py:37-40: np.array(poly) is float64; x' = width - x - 1 in double, one rounding per subtraction"""
+    out = [float(v) for v in poly]
+    out[0::2] = [float(width) - x - 1.0 for x in out[0::2]]
+    return out
+
+
+def flip_rles(rles, height, width, device="cuda"):
+    """RLE dicts (counts: an uncompressed list or a compressed str / bytes, as pack_gt_masks takes them) of one height x width image
+    -> their left/right mirror images as dict(size=[height, width], counts=<the compressed string>), by dtc_flip_rle.  Loader code:
+    it syncs for `need`, and calls again when a mirrored list is longer than the first guess."""
+    if not rles:
+        return []
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("detectorch_amd flips run lists on the GPU only (got device %s); there is no CPU fallback" % dev)
+    height, width = int(height), int(width)
+    packed = pack_gt_masks([list(rles)], [(height, width)], dev)
+    runs, n_runs = packed["gt_runs"], packed["gt_n_runs"]
+    im_size = torch.tensor([[height, width]], dtype=torch.float32, device=dev)
+    res = hip_flip.flip_rle(runs, n_runs, im_size, [1])
+    need = res["need"].cpu().numpy()                           # the one sync
+    if int(need.max(initial=0)) > res["out_runs"].shape[2]:
+        res = hip_flip.flip_rle(runs, n_runs, im_size, [1], out_stride=int(need.max()))
+    n = res["out_n_runs"][0].cpu().numpy()
+    out_runs = res["out_runs"][0].cpu().numpy().view(np.uint32)
+    out = []
+    for j in range(len(rles)):
+        if n[j] < 0:
+            raise ValueError("flip_segms: RLE %d does not describe a %d x %d mask (its runs must sum to height * width <= 2^30)" % (
+                j, height, width))
+        out.append(dict(size=[height, width], counts=result_utils._rle_counts_to_string(out_runs[j, :n[j]].astype(np.int64).tolist())))
+    return out
+
+
+def flip_segms(segms, height, width, device="cuda"):
+    """The reference's segms.flip_segms: left/right flip each segmentation of a list, all of one height x width image.  A list of
+    polygons is mirrored in Python doubles (no GPU needed); an RLE dict -- `counts` an uncompressed list or a compressed string --
+    is mirrored on the device and comes back as dict(size, counts=<compressed string>), what the reference's encode returns."""
+    rle_at = [i for i, segm in enumerate(segms) if not is_polygons(segm)]
+    for i in rle_at:
+        assert isinstance(segms[i], dict), "a segmentation is a list of polygons or an RLE dict"
+    rles = iter(flip_rles([segms[i] for i in rle_at], height, width, device))
+    return [[_flip_poly(poly, width) for poly in segm] if is_polygons(segm) else next(rles) for segm in segms]
