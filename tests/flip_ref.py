@@ -4,6 +4,7 @@
     flip_boxes       lib/utils/boxes.py:264-269, lib/data/roidb.py:112-117            float32
     flip_poly        lib/utils/segms.py:37-40                                          float64
     flip_rle_runs    lib/utils/segms.py:42-50 (decode, mask[:, ::-1], encode)          written from COCO's format definition
+    flip_rle_sparse  the same on intervals, no bitmap (images of up to 2^30 pixels)    held to flip_rle_runs by tests/test_flip_limits_host.py
     flip_image       lib/data/coco_dataset.py:51-53                                    image[:, ::-1, :]
 
 pycocotools is not installed where this is tested: the run-list coding is written from the format definition (column-major, runs
@@ -70,6 +71,49 @@ def flip_rle_runs(runs, h, w):
     return encode(decode(runs, h, w)[:, ::-1])
 
 
+def cut(runs, h, w):
+    """the runs cut at the column boundaries -> [(value, start, end)] in input order: of every run of at least one pixel its head (up
+    to the end of its first column), the whole columns in its middle as ONE piece, and its tail; a piece starts at a multiple of h or
+    is the head of a run that starts inside a column"""
+    out, s = [], 0
+    for k, n in enumerate(int(v) for v in runs):
+        e = s + n
+        if n > 0:
+            c0, c1 = s // h, (e - 1) // h
+            out.append((k & 1, s, min(e, (c0 + 1) * h)))
+            if c1 > c0 + 1:
+                out.append((k & 1, (c0 + 1) * h, c1 * h))
+            if c1 > c0:
+                out.append((k & 1, c1 * h, e))
+        s = e
+    return out
+
+
+def flip_rle_sparse(runs, h, w):
+    """flip_rle_runs without a bitmap: the pieces of the one-runs, [c h + y0, c h + y1) -> [(w - 1 - c) h + y0, (w - 1 - c) h + y1)
+    (the whole columns c0 .. c1 - 1 of a piece to w - c1 .. w - 1 - c0), sorted, touching pieces merged, canonical runs out"""
+    hw = h * w
+    assert sum(int(v) for v in runs) == hw, (sum(int(v) for v in runs), h, w)
+    if hw == 0:
+        return [0]
+    mapped = []
+    for v, s, e in cut(runs, h, w):
+        if v:
+            c0, c1 = s // h, (e - 1) // h                      # c1 > c0: whole columns only
+            mapped.append(((w - 1 - c1) * h + s - c0 * h, (w - 1 - c1) * h + e - c0 * h))
+    merged = []
+    for a, b in sorted(mapped):
+        if merged and a == merged[-1][1]:
+            merged[-1][1] = b
+        else:
+            merged.append([a, b])
+    bounds = [x for ab in merged for x in ab]
+    if bounds and bounds[-1] == hw:
+        bounds.pop()
+    edges = [0] + bounds + [hw]
+    return [q - p for p, q in zip(edges[:-1], edges[1:])]
+
+
 def side(v):
     """one side of im_size as the kernels read it: truncated; below 1, NaN: 0; above 2^30: 2^30"""
     v = np.float32(v)
@@ -78,9 +122,10 @@ def side(v):
     return 1 << 30 if v >= np.float32(1 << 30) else int(v)
 
 
-def flip_rle_batched(runs, n_runs, im_size, flipped, out_stride, counts=None):
+def flip_rle_batched(runs, n_runs, im_size, flipped, out_stride, counts=None, flip=None):
     """the batched entry: runs uint32-valued [N, R, S], n_runs [N, R] -> (lists per row or None where nothing is written, out_n_runs
-    [N, R], need [N, R]); rows past counts are None / left 0 in the arrays"""
+    [N, R], need [N, R]); rows past counts are None / left 0 in the arrays; `flip`: flip_rle_runs (the default) or flip_rle_sparse"""
+    flip = flip or flip_rle_runs
     N, R, S = np.asarray(runs).shape
     runs = np.asarray(runs).astype(np.int64) & 0xffffffff
     lists = [[None] * R for _ in range(N)]
@@ -102,7 +147,7 @@ def flip_rle_batched(runs, n_runs, im_size, flipped, out_stride, counts=None):
                 out_n[n, r], need[n, r] = -1, 0
                 continue
             else:
-                res = flip_rle_runs(row, h, w)
+                res = flip(row, h, w)
             need[n, r] = len(res)
             if len(res) <= out_stride:
                 out_n[n, r], lists[n][r] = len(res), res

@@ -8,6 +8,7 @@ per instance, and a run-length coding of the column-major bitmap that does not u
     row               one gt row of a case -> None (takes part in nothing) or (flat bitmap, events)
     runs_of           flat bitmap -> COCO's uncompressed run lengths
     run               a whole case -> what dtc_poly_rle must write: n_runs, runs (lists), area, need
+    run_sparse        the same without a bitmap: spans of sorted events, united per row (images of up to 2^30 pixels)
     even_odd_hw       the independent check of tests/mask_train_ref.even_odd, for h x w
 
 COCO's own code (pycocotools) is not available: the rule is restated from the published algorithm (common/maskApi.c:rleFrPoly,
@@ -32,8 +33,9 @@ def pixels(im_size):
     return min(side(im_size[0]) * side(im_size[1]), MAX_PIXELS)
 
 
-def trace_positions(xy, h, w):
-    """xy [n, 2] float64 -> int64 array of the toggled positions, in trace order"""
+def trace_positions(xy, h, w, dropped=None):
+    """xy [n, 2] float64 -> int64 array of the toggled positions, in trace order; `dropped`: a list that receives the candidate
+    positions that were not below h w"""
     xy = np.asarray(xy, np.float64)
     X = (5.0 * xy[:, 0] + 0.5).astype(np.int64)                # astype: C's (int), toward zero
     Y = (5.0 * xy[:, 1] + 0.5).astype(np.int64)
@@ -65,6 +67,8 @@ def trace_positions(xy, h, w):
         j = np.ceil(np.minimum(np.maximum((vs + 0.5) / 5.0 - 0.5, 0.0), float(h))).astype(np.int64)
         pos = i * h + j
         out.append(pos[pos < hw])
+        if dropped is not None:
+            dropped.extend(pos[pos >= hw].tolist())
     return np.concatenate(out) if out else np.zeros(0, np.int64)
 
 
@@ -147,6 +151,67 @@ def run(case, runs_stride, events_stride):
                 continue
             n_runs[n, g], area[n, g], runs[n][g] = len(rl), int(flat.sum()), rl
     return dict(n_runs=n_runs, runs=runs, area=area, need=need, bitmaps=bitmaps)
+
+
+def row_events(case, n, g):
+    """None: the row takes part in nothing; else the event positions of each of its polygons that is traced (int64 arrays): row()
+    without the bitmap"""
+    G = case["gt_poly_ptr"].shape[1] - 1
+    h, w = side(case["im_size"][n, 0]), side(case["im_size"][n, 1])
+    if g >= min(max(int(case["gt_counts"][n]), 0), G) or h * w == 0 or case["poly_ptr"].shape[1] < 2 or case["poly_xy"].shape[1] == 0:
+        return None
+    polys = valid_polys(case, n, g)
+    if not polys:
+        return None
+    return [trace_positions(p, h, w) for p in polys if (np.abs(p) < COORD_LIMIT).all()]
+
+
+def spans_of(events, hw):
+    """the event positions of one polygon -> its half-open spans [a, b): the sorted events paired, an odd last one runs to hw"""
+    ev = sorted(int(v) for v in events)
+    if len(ev) % 2:
+        ev.append(hw)
+    return [(a, b) for a, b in zip(ev[0::2], ev[1::2]) if a < b]
+
+
+def union_runs(spans, hw):
+    """spans of several polygons -> (run lengths of their union over [0, hw), its area), in Python integers"""
+    merged = []
+    for a, b in sorted(spans):
+        if merged and a <= merged[-1][1]:
+            merged[-1][1] = max(merged[-1][1], b)
+        else:
+            merged.append([a, b])
+    bounds = [v for ab in merged for v in ab]
+    if bounds and bounds[-1] == hw:
+        bounds.pop()
+    edges = [0] + bounds + [hw]
+    return [q - p for p, q in zip(edges[:-1], edges[1:])], sum(b - a for a, b in merged)
+
+
+def run_sparse(case, runs_stride, events_stride):
+    """run() without a bitmap -> dict(n_runs, runs, area, need) as run() gives them: per polygon the spans of its sorted events, per
+    row their union; nothing here is sized by h w"""
+    N, G = case["gt_poly_ptr"].shape[0], case["gt_poly_ptr"].shape[1] - 1
+    n_runs, area, need = np.zeros((N, G), np.int32), np.zeros((N, G), np.int32), np.zeros((N, G, 2), np.int32)
+    runs = [[None] * G for _ in range(N)]
+    for n in range(N):
+        hw = pixels(case["im_size"][n])
+        for g in range(G):
+            per_poly = row_events(case, n, g)
+            if per_poly is None:
+                continue
+            events = sum(len(e) for e in per_poly)
+            if events > events_stride:
+                n_runs[n, g], need[n, g] = -1, (events, -1)
+                continue
+            rl, ones = union_runs([s for e in per_poly for s in spans_of(e, hw)], hw)
+            need[n, g] = (events, len(rl))
+            if len(rl) > runs_stride:
+                n_runs[n, g] = -1
+                continue
+            n_runs[n, g], area[n, g], runs[n][g] = len(rl), ones, rl
+    return dict(n_runs=n_runs, runs=runs, area=area, need=need)
 
 
 def pack(polys_per_image, G=None, PTS=None, NP=None, dtype=np.float64):
