@@ -11,7 +11,8 @@ operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so), build_optim() for the 
 (csrc/eval/*.hip -> libdetectorch_eval_hip.so), build_segm() for scoring masks: RLE mask IoU and the match on it
 (csrc/segm_eval/*.hip -> libdetectorch_segm_hip.so), build_poly() for ground-truth polygons at image size to run lists
 (csrc/poly_rle/*.hip -> libdetectorch_poly_hip.so), build_flip() for the horizontal-flip augmentation: mirrored network input, boxes,
-polygons and run lists (csrc/flip/*.hip -> libdetectorch_flip_hip.so).
+polygons and run lists (csrc/flip/*.hip -> libdetectorch_flip_hip.so), build_mpost() for mask post-processing on run lists: mask
+boxes, mask overlaps, mask NMS and mask voting (csrc/mask_post/*.hip -> libdetectorch_mpost_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -83,10 +84,10 @@ def build(force=False, verbose=False):
 # the head losses with their gradients (include/detectorch_loss_hip.h), the gradients of the region operators
 # (include/detectorch_grad_hip.h), the clipped SGD step (include/detectorch_optim_hip.h), RPN training
 # (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h), scoring (include/detectorch_eval_hip.h), scoring
-# masks (include/detectorch_segm_hip.h), polygons to run lists (include/detectorch_poly_hip.h) and the horizontal flip
-# (include/detectorch_flip_hip.h).  sources()
+# masks (include/detectorch_segm_hip.h), polygons to run lists (include/detectorch_poly_hip.h), the horizontal flip
+# (include/detectorch_flip_hip.h) and mask post-processing (include/detectorch_mpost_hip.h).  sources()
 # globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip, csrc/optim/*.hip, csrc/rpn_train/*.hip, csrc/mask_train/*.hip,
-# csrc/eval/*.hip, csrc/segm_eval/*.hip, csrc/poly_rle/*.hip and csrc/flip/*.hip include the csrc/ headers by include path and are built with the same
+# csrc/eval/*.hip, csrc/segm_eval/*.hip, csrc/poly_rle/*.hip, csrc/flip/*.hip and csrc/mask_post/*.hip include the csrc/ headers by include path and are built with the same
 # FLAGS, one library per directory.
 TRAIN_CSRC = os.path.join(CSRC, "train")
 TRAIN_LIB = os.path.join(LIBDIR, "libdetectorch_train_hip.so")
@@ -108,6 +109,8 @@ POLY_CSRC = os.path.join(CSRC, "poly_rle")                   # gt polygons at im
 POLY_LIB = os.path.join(LIBDIR, "libdetectorch_poly_hip.so")
 FLIP_CSRC = os.path.join(CSRC, "flip")                       # horizontal-flip augmentation (include/detectorch_flip_hip.h): input blob, boxes, polygons, RLE
 FLIP_LIB = os.path.join(LIBDIR, "libdetectorch_flip_hip.so")
+MPOST_CSRC = os.path.join(CSRC, "mask_post")                 # mask post-processing on run lists (include/detectorch_mpost_hip.h): boxes, overlaps, NMS, voting
+MPOST_LIB = os.path.join(LIBDIR, "libdetectorch_mpost_hip.so")
 
 
 def _side_sources(csrc):
@@ -189,6 +192,10 @@ def build_flip(force=False, verbose=False):
     return _build_side(FLIP_LIB, FLIP_CSRC, force, verbose)
 
 
+def build_mpost(force=False, verbose=False):
+    return _build_side(MPOST_LIB, MPOST_CSRC, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
@@ -201,3 +208,4 @@ if __name__ == "__main__":
     print(build_segm(force="--force" in sys.argv, verbose=True))
     print(build_poly(force="--force" in sys.argv, verbose=True))
     print(build_flip(force="--force" in sys.argv, verbose=True))
+    print(build_mpost(force="--force" in sys.argv, verbose=True))

@@ -166,7 +166,7 @@ status dtc_soft_nms(dets n:i sigma:f overlap_thresh:f score_thresh:f method:i de
 status dtc_bbox_transform(boxes deltas n:i n_cls:i wx:f wy:f ww:f wh:f do_clip:i im_h:f im_w:f out stream)
 """
 
-_KINDS = {"p": C.c_void_p, "i": C.c_int, "f": C.c_float, "z": C.c_size_t, "q": C.c_longlong}
+_KINDS = {"p": C.c_void_p, "i": C.c_int, "f": C.c_float, "z": C.c_size_t, "q": C.c_longlong, "d": C.c_double}
 _RETURNS = {"status": C.c_int, "int": C.c_int, "size": C.c_size_t, "str": C.c_char_p, "void": None}
 
 
@@ -181,7 +181,7 @@ def _as_is(v):
     return v
 
 
-_CONVERT = {"p": _pointer, "i": int, "f": float, "z": int, "q": int}
+_CONVERT = {"p": _pointer, "i": int, "f": float, "z": int, "q": int, "d": float}
 
 
 def signatures(rows, structs):

@@ -12,13 +12,17 @@ itself is unpinned (tests/README_poly_rle.md).
 flip_segms is the reference's (segms.py:35-61): polygon lists are mirrored in Python doubles -- a list is loader data, and it is the
 arithmetic of dtc_flip_polygons --, RLE dicts go through dtc_flip_rle (hip_flip.py), which mirrors the run list without a bitmap.
 
-There is no CPU fallback: a polygon to convert, or an RLE to flip, needs a GPU.  polys_to_mask_wrt_box is csrc/mask_train's
-(mask_rcnn_targets.py); the rle_mask_* functions of the reference are out of scope.
+rle_mask_nms, rle_mask_voting and rle_masks_to_boxes are the reference's (segms.py:134-268) on dtc_mpost_* (hip_mpost.py,
+include/detectorch_mpost_hip.h): overlaps, the greedy walk, the vote and the boxes are computed on the run lists, without a bitmap.
+The *_batched forms take the device tensors of hip.mask_rle as they are and do not sync.
+
+There is no CPU fallback: a polygon to convert, an RLE to flip, masks to suppress, vote or box need a GPU.  polys_to_mask_wrt_box is
+csrc/mask_train's (mask_rcnn_targets.py).
 """
 import numpy as np
 import torch
 
-from .. import hip_flip, hip_poly
+from .. import hip_flip, hip_mpost, hip_poly
 from . import result_utils
 from .evaluator import pack_gt_masks
 from .mask_rcnn_targets import pack_polygons
@@ -217,3 +221,139 @@ def flip_segms(segms, height, width, device="cuda"):
         assert isinstance(segms[i], dict), "a segmentation is a list of polygons or an RLE dict"
     rles = iter(flip_rles([segms[i] for i in rle_at], height, width, device))
     return [[_flip_poly(poly, width) for poly in segm] if is_polygons(segm) else next(rles) for segm in segms]
+
+
+# ---- mask NMS, mask voting, mask boxes (the reference's segms.py:134-268) on run lists ----------------------------------------------------
+def rle_masks_to_boxes_batched(runs, n_runs, im_size, counts=None, out=None):
+    """rle_masks_to_boxes on device tensors in hip.mask_rle's layout: runs i32 [N,R,stride] (the uint32 run lengths), n_runs i32
+    [N,R], im_size f32 [N,2] = (h, w), counts i32 [N] or None.  -> dict(boxes i32 [N,R,4] = the inclusive (x0, y0, x1, y1), zeros for
+    an empty mask; area i32 [N,R]; nonempty i32 [N,R], the reference's `keep`).  `out`: the dict of an earlier call.  No host sync."""
+    return hip_mpost.mask_boxes(runs, n_runs, im_size, counts, out=out)
+
+
+def _pick(out, keys):
+    return None if out is None else {k: out[k] for k in keys}
+
+
+def rle_mask_nms_batched(runs, n_runs, dets, count, im_size, thresh, mode='IOU', out=None, ws=None):
+    """rle_mask_nms on device tensors: runs i32 [N,R,stride] / n_runs i32 [N,R] (hip.mask_rle's), dets f32 [N,R,6] (score in column
+    4, class in column 5: rows suppress rows of their own class only), count i32 [N], im_size f32 [N,2].  -> dict(keep i32 [N,R]: the
+    kept rows in the order kept, then -1; keep_count i32 [N]; ovr f64 [N,R,R]: maskUtils.iou of the masks with themselves, with crowd
+    for IOMA and CONTAINMENT; a_area, b_area i32 [N,R]: the masks' areas).  `out`: the dict of an earlier call, written in place;
+    `ws`: a uint8 workspace (hip_mpost.overlaps_workspace_bytes).  No host sync."""
+    if mode not in hip_mpost.NMS_MODES:
+        raise NotImplementedError('Mode {} is unknown'.format(mode))
+    pairs = hip_mpost.mask_overlaps(runs, n_runs, count, runs, n_runs, count, im_size, crowd=mode != 'IOU',
+                                    out=_pick(out, ("ovr", "a_area", "b_area")), ws=ws)
+    kept = hip_mpost.mask_nms(dets, count, pairs["ovr"], thresh, mode, out=_pick(out, ("keep", "keep_count")))
+    return dict(kept, **pairs)
+
+
+def rle_mask_voting_batched(top_runs, top_n_runs, top_count, all_runs, all_n_runs, all_dets, all_count, im_size, iou_thresh,
+                            binarize_thresh, method='AVG', out_stride=None, out=None, ws=None):
+    """rle_mask_voting on device tensors: the top masks (top_runs i32 [N,T,stride], top_n_runs i32 [N,T], top_count i32 [N]) are
+    replaced by the vote of the masks of the pool (all_runs i32 [N,A,stride'], all_n_runs i32 [N,A], all_dets f32 [N,A,5 or more]:
+    box and score, all_count i32 [N]) that overlap them by iou_thresh or more.  -> dict(out_runs i32 [N,T,out_stride], out_n_runs i32
+    [N,T]: -1 where a list did not fit, need i32 [N,T]: what it takes; ovr f64 [N,T,A], a_area i32 [N,T], b_area i32 [N,A]: the
+    overlaps and areas of tops and pool).  `out`: the dict of an earlier call, written in place; `ws`: a uint8 workspace of at least
+    rle_mask_voting_workspace_bytes(...).  No host sync."""
+    if method not in hip_mpost.VOTE_METHODS:
+        raise NotImplementedError('Method {} is unknown'.format(method))
+    pairs = hip_mpost.mask_overlaps(top_runs, top_n_runs, top_count, all_runs, all_n_runs, all_count, im_size, crowd=False,
+                                    out=_pick(out, ("ovr", "a_area", "b_area")), ws=ws)
+    voted = hip_mpost.mask_vote(top_runs, top_n_runs, top_count, all_runs, all_n_runs, all_dets, all_count, pairs["ovr"], im_size,
+                                iou_thresh, binarize_thresh, method, out_stride=out_stride,
+                                out=_pick(out, ("out_runs", "out_n_runs", "need")), ws=ws)
+    return dict(voted, **pairs)
+
+
+def rle_mask_voting_workspace_bytes(N, T, top_stride, A, all_stride):
+    """the bytes of the `ws` that serves both stages of rle_mask_voting_batched (they run one after the other on one stream)"""
+    return max(hip_mpost.overlaps_workspace_bytes(N, T, top_stride, A, all_stride), hip_mpost.vote_workspace_bytes(N, A, all_stride))
+
+
+def _pack_one_image(masks, dev, what):
+    """RLE dicts of one image -> (runs i32 [1,n,stride], n_runs i32 [1,n], count i32 [1], im_size f32 [1,2], [h, w])"""
+    if dev.type != "cuda":
+        raise RuntimeError("detectorch_amd runs %s on the GPU only (got device %s); there is no CPU fallback" % (what, dev))
+    size = [int(v) for v in masks[0]['size']]
+    for j, m in enumerate(masks):
+        if [int(v) for v in m['size']] != size:
+            raise ValueError("%s: mask %d is %s, mask 0 is %s: the masks of one call are of one image" % (what, j, list(m['size']), size))
+    if len(masks) > hip_mpost.MAX_ROWS:
+        raise ValueError("%s: at most %d masks in one call, got %d" % (what, hip_mpost.MAX_ROWS, len(masks)))
+    packed = pack_gt_masks([list(masks)], [size], dev)
+    count = torch.tensor([len(masks)], dtype=torch.int32, device=dev)
+    return packed["gt_runs"], packed["gt_n_runs"], count, torch.tensor([size], dtype=torch.float32, device=dev), size
+
+
+def rle_mask_nms(masks, dets, thresh, mode='IOU', device="cuda"):
+    """The reference's segms.rle_mask_nms: greedy non-maximum suppression by mask overlap.  masks: RLE dicts (counts: an uncompressed
+    list or a compressed str / bytes) of one image; dets [n, 5 or more], the score in column 4; mode 'IOU', 'IOMA' (intersection over
+    the smaller area) or 'CONTAINMENT' (ious[m1, m2] = |m1 & m2| / area(m1)).  -> the list of kept indices by descending score;
+    equal scores go by index (the reference's unstable argsort leaves them unspecified)."""
+    if len(masks) == 0:
+        return []
+    if len(masks) == 1:
+        return [0]
+    if mode not in hip_mpost.NMS_MODES:
+        raise NotImplementedError('Mode {} is unknown'.format(mode))
+    dev = torch.device(device)
+    runs, n_runs, count, im_size, _ = _pack_one_image(masks, dev, "rle_mask_nms")
+    rows = np.zeros((1, len(masks), 6), np.float32)
+    rows[0, :, 4] = np.asarray(dets, np.float32).reshape(len(masks), -1)[:, 4]
+    rows[0, :, 5] = 1.0
+    res = rle_mask_nms_batched(runs, n_runs, torch.from_numpy(rows).to(dev), count, im_size, float(thresh), mode)
+    k = int(res["keep_count"][0])
+    return [int(v) for v in res["keep"][0, :k].cpu().numpy()]
+
+
+def rle_mask_voting(top_masks, all_masks, all_dets, iou_thresh, binarize_thresh, method='AVG', device="cuda"):
+    """The reference's segms.rle_mask_voting: new masks, in correspondence with top_masks, from the masks of all_masks that overlap
+    them by iou_thresh or more: 'AVG' binarizes their average, weighted by the score inside each voter's box and 1e-5 outside,
+    'UNION' joins them.  Masks are RLE dicts of one image; all_dets [n, 5 or more]: box and score.  -> a list of RLE dicts: a voted
+    mask as dict(size, counts=<compressed string>); a top mask that is empty or has fewer than two voters comes back as the caller's
+    own dict, as in the reference.  No top masks: None, as in the reference.  Loader code: it syncs, and votes again when a voted
+    list is longer than the first guess."""
+    if method not in hip_mpost.VOTE_METHODS:
+        raise NotImplementedError('Method {} is unknown'.format(method))
+    if len(top_masks) == 0:
+        return None
+    if len(all_masks) == 0:                                    # nobody votes (the reference fails here)
+        return list(top_masks)
+    dev = torch.device(device)
+    t_runs, t_n, t_count, im_size, size = _pack_one_image(top_masks, dev, "rle_mask_voting")
+    a_runs, a_n, a_count, _, a_size = _pack_one_image(all_masks, dev, "rle_mask_voting")
+    if a_size != size:
+        raise ValueError("rle_mask_voting: top masks of %s and a pool of %s" % (size, a_size))
+    d = np.asarray(all_dets, np.float32).reshape(len(all_masks), -1)
+    if d.shape[1] < 5:
+        raise ValueError("rle_mask_voting: all_dets [n, 5 or more], got %s" % (d.shape,))
+    d = torch.from_numpy(np.ascontiguousarray(d[None])).to(dev)
+    args = (t_runs, t_n, t_count, a_runs, a_n, d, a_count, im_size, float(iou_thresh), float(binarize_thresh), method)
+    res = rle_mask_voting_batched(*args, out_stride=max(t_runs.shape[2], a_runs.shape[2]))
+    need = res["need"].cpu().numpy()                           # the one sync
+    if int(need.max(initial=0)) > res["out_runs"].shape[2]:
+        res = rle_mask_voting_batched(*args, out_stride=int(need.max()))
+    n = res["out_n_runs"][0].cpu().numpy()
+    out_runs = res["out_runs"][0].cpu().numpy().view(np.uint32)
+    ovr, area = res["ovr"][0].cpu().numpy(), res["a_area"][0].cpu().numpy()
+    out = []
+    for j, top in enumerate(top_masks):
+        if n[j] < 0:
+            raise ValueError("rle_mask_voting: top mask %d does not describe a %d x %d mask of at most 2^30 pixels" % (j, size[0], size[1]))
+        if area[j] == 0 or int((ovr[j, :len(all_masks)] >= float(iou_thresh)).sum()) < 2:
+            out.append(top)                                   # copied as it is: the caller's own dict
+        else:
+            out.append(dict(size=list(size), counts=result_utils._rle_counts_to_string(out_runs[j, :n[j]].astype(np.int64).tolist())))
+    return out
+
+
+def rle_masks_to_boxes(masks, device="cuda"):
+    """The reference's segms.rle_masks_to_boxes: masks: RLE dicts of one image -> (boxes float64 [n, 4], the inclusive (x0, y0, x1,
+    y1) of every mask, zeros for an empty one; the indices of the masks that are not empty).  No masks: []."""
+    if len(masks) == 0:
+        return []
+    runs, n_runs, count, im_size, _ = _pack_one_image(masks, torch.device(device), "rle_masks_to_boxes")
+    res = rle_masks_to_boxes_batched(runs, n_runs, im_size, count)
+    return res["boxes"][0].cpu().numpy().astype(np.float64), np.where(res["nonempty"][0].cpu().numpy() != 0)[0]
