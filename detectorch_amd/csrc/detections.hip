@@ -32,6 +32,7 @@
 #include "iou_threshold.h"
 #include "radix_select.h"
 #include "soft_nms_walk.h"
+#include "softmax_fold.h"
 #include "wave_ops.h"
 
 namespace dtc {
@@ -81,15 +82,9 @@ constexpr int kCandWords = 64;   // bitmap words per segment: R <= 4096
 __global__ __launch_bounds__(kDetThreads) void det_softmax_stats_kernel(const float* logits, int n_rows, int n_cls, double* stats) {
   const int row = blockIdx.x * (kDetThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n_rows) return;
-  const float* l = logits + (size_t)row * n_cls;
-  float m = -INFINITY;
-  for (int j = lane; j < n_cls; j += 64) m = fmaxf(m, l[j]);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  double e = 0.0;
-  for (int j = lane; j < n_cls; j += 64) e += exp((double)l[j] - (double)m);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) e += __shfl_xor(e, off, 64);       // lane 0: ((s0+s32)+(s16+s48))+... halving tree
+  float m;
+  double e;
+  softmax_row_stats(logits + (size_t)row * n_cls, n_cls, lane, m, e);
   if (lane == 0) { stats[(size_t)row * 2] = (double)m; stats[(size_t)row * 2 + 1] = e; }
 }
 
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(kDetThreads) void det_candidates_kernel(DetParams p
         sv[u] = sc[(size_t)r * p.n_cls];
         if (p.sm_stats) {      // logits in: softmax column formed here (detector.py:281)
           const double* st = p.sm_stats + ((size_t)b * p.R + r) * 2;
-          sv[u] = (float)(exp((double)sv[u] - st[0]) / st[1]);
+          sv[u] = DTC_SOFTMAX_PROB(sv[u], st);
         }
       }
     }

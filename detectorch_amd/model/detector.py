@@ -602,10 +602,11 @@ class detector(nn.Module):
         return super().load_state_dict(*args, **kw)
 
     # ---- batched entry: B images, zero host round trips ------------------------------------------------------------------
-    def _region_path(self, B, h, w, dev, det_options=None, top_n=1000):
+    def _region_path(self, B, h, w, dev, det_options=None, top_n=1000, view=None):
         from ..pipeline import C4RegionPath, FpnRegionPath
-        # the detection options are baked into the path's launches (and its captured graph): part of the key
-        key = (B, h, w, str(dev), self.max_out, tuple(sorted((det_options or {}).items())), top_n)
+        # the detection options are baked into the path's launches (and its captured graph): part of the key; so is the view of a
+        # test-time-augmented call (utils/test_aug.py), whose views of one blob size must not share their buffers
+        key = (B, h, w, str(dev), self.max_out, tuple(sorted((det_options or {}).items())), top_n) + (() if view is None else (view,))
         if key in self._paths:
             self._paths[key] = self._paths.pop(key)          # most recently used last
         else:
@@ -652,10 +653,11 @@ class detector(nn.Module):
         counts = torch.as_tensor(proposal_counts).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
         return proposals, counts
 
-    def _box_stages(self, path, rpn, props, feats, img_features, sf, sz, blob_hw):
+    def _box_stages(self, path, rpn, props, feats, img_features, sf, sz, blob_hw, detect=True):
         """The middle both flavours of forward_batched share: bind the proposal inputs -- rpn = (scores, deltas) of the model's RPN
         head (per level for FPN), or props = (boxes, counts) precomputed -- and the feature maps RoIAlign reads, launch_proposals,
-        box head -> cls / bbox, launch_detections; the head outputs stay on the path for per_image()."""
+        box head -> cls / bbox, launch_detections; the head outputs stay on the path for per_image().  detect=False stops in front
+        of launch_detections: a view of a test-time-augmented call, whose detections come from all views together."""
         if props is not None:
             path.bind_proposals(*props, sf, feats)
         else:
@@ -667,11 +669,12 @@ class detector(nn.Module):
         cls_logits = self.classif_head(x).reshape(B, T, -1).contiguous()
         bbox_pred = self.bbox_head(x).reshape(B, T, -1).contiguous()
         path.bind_heads(cls_logits, bbox_pred, sf, sz)
-        path.launch_detections()
         path.img_features, path.cls_logits_out, path.bbox_pred_out = img_features, cls_logits, bbox_pred
+        if detect:
+            path.launch_detections()
 
     @torch.no_grad()
-    def _forward_batched_c4(self, images, sf, sz, blob_hw, det_options, proposals, proposal_counts):
+    def _forward_batched_c4(self, images, sf, sz, blob_hw, det_options, proposals, proposal_counts, view=None):
         """C4 models (e2e Faster / Mask R-CNN R-50-C4, Fast R-CNN R-50-C4): res4 -> C4RegionPath stages -> res5 head -> detections
         -> shared res5 + deconv + classifier -> paste (M = 14) + RLE."""
         if (getattr(self, "_opt_dtype", None) is not None or self.channels_last or self.backbone_dtype not in (None, torch.float32)
@@ -687,19 +690,40 @@ class detector(nn.Module):
         else:
             rpn_cls, rpn_bbox = self.rpn(img_features, logits=self.fuse_rpn_sigmoid)
             rpn = (rpn_cls.float().contiguous(), rpn_bbox.float().contiguous())
-        path = self._region_path(B, h, w, dev, det_options, 1000 if props is None else int(props[0].shape[1]))
-        self._box_stages(path, rpn, props, img_features, img_features, sf, sz, blob_hw)    # head: res5 + avgpool, [B*T, 2048]
-        if self.use_mask_head:
-            mh = self.mask_head                                                     # detector.py:99-112, the non-FPN branch
-            m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(path.mask_feats))))
-            path.bind_masks((torch.sigmoid(m) if mh.output_prob else m).contiguous())        # [B*max_out, 81, 14, 14]
+        path = self._region_path(B, h, w, dev, det_options, 1000 if props is None else int(props[0].shape[1]), view)
+        self._box_stages(path, rpn, props, img_features, img_features, sf, sz, blob_hw, detect=view is None)    # head: res5 + avgpool, [B*T, 2048]
+        if self.use_mask_head and view is None:
+            path.bind_masks(self._mask_probs(path.mask_feats))                      # [B*max_out, 81, 14, 14]
             path.launch_masks()
         return path
+
+    def _mask_probs(self, mask_feats):
+        """The mask head on a path's pooled mask features [B*max_out, C, 14, 14] -> class probabilities [B*max_out, n_cls, M, M]
+        (M = 28 for FPN, 14 for C4), contiguous float32: what bind_masks takes."""
+        mh = self.mask_head
+        if not self.use_fpn_body:                                                   # detector.py:99-112, the non-FPN branch
+            m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(mask_feats))))
+            return (torch.sigmoid(m) if mh.output_prob else m).contiguous()
+        opt = getattr(self, "_opt_dtype", None)
+        if opt is not None:
+            m = hip.bias_act_(_conv_nobias(mh.transposed_conv, mh.conv_head(mask_feats.to(opt))), _ebias(mh.transposed_conv))
+            # class logits: bias-free 1x1 conv, then bias + widening + NCHW layout in ONE pass, sigmoid in place
+            y = _conv_nobias(mh.classif_logits, m)
+            return torch.add(y, _ebias(mh.classif_logits).view(1, -1, 1, 1),
+                             out=torch.empty(y.shape, dtype=torch.float32, device=y.device)).sigmoid_()
+        if self.head_dtype is not None and self.head_dtype != torch.float32:        # mask-head convs in the pooled features' type
+            with torch.autocast("cuda", dtype=self.head_dtype):
+                m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(mask_feats.to(self.head_dtype)))))
+            m = m.float()
+        else:
+            m = mh.conv_head(mask_feats.float() if mask_feats.dtype != torch.float32 else mask_feats)
+            m = mh.classif_logits(mh.relu(mh.transposed_conv(m)))
+        return torch.sigmoid(m).contiguous()
 
     @torch.no_grad()
     def forward_batched(self, images, scaling_factor, im_size, blob_hw=None, do_soft_nms=False, soft_nms_sigma=0.5,
                         soft_nms_method='linear', do_bbox_vote=False, bbox_vote_thresh=0.8, proposals=None, proposal_counts=None,
-                        bbox_vote_method='ID'):
+                        bbox_vote_method='ID', view=None):
         """Mask / Faster R-CNN FPN forward for a BATCH (lib/model/detector.py:233-286 + :99-112 + eval_mask_FPN.ipynb:231-262,
         which the reference runs image by image with 21 synchronising copies each).
           images [B,3,H,W] prepared blobs of one padded size (utils.blob.im_list_to_blob); scaling_factor [B]; im_size [B,2]
@@ -721,7 +745,10 @@ class detector(nn.Module):
         proposals [B,N,4] (original-image coordinates; or a list of B [n_b,4] arrays) + proposal_counts [B] (default: all N): the
         precomputed proposals of a model WITHOUT an RPN head (Fast R-CNN C4 / FPN; required there, rejected with one).  Scaled by
         scaling_factor, deduplicated on the 1/16 grid and distributed over the levels on the device (dtc_prepare_proposals:
-        preprocess_sample.py:35-45); N <= 2048."""
+        preprocess_sample.py:35-45); N <= 2048.
+        view (utils/test_aug.py): not None makes this call one VIEW of a test-time-augmented batch -- it gets a region path of its
+        own under that key and stops after the box-head outputs (path.cls_logits_out / bbox_pred_out on path.rois5): no detection
+        stage, no mask branch."""
         if self.use_rpn_head and proposals is not None:
             raise ValueError("this model has an RPN head: its proposals come from it (proposals= is for models without one)")
         if not self.use_rpn_head and proposals is None:
@@ -739,7 +766,7 @@ class detector(nn.Module):
         sf = torch.as_tensor(scaling_factor, dtype=torch.float32, device=dev).reshape(B).contiguous()
         sz = torch.as_tensor(im_size, dtype=torch.float32, device=dev).reshape(B, 2).contiguous()
         if not self.use_fpn_body:
-            return self._forward_batched_c4(images, sf, sz, blob_hw, det_options, proposals, proposal_counts)
+            return self._forward_batched_c4(images, sf, sz, blob_hw, det_options, proposals, proposal_counts, view)
         if not self.use_two_layer_mlp_head:
             raise NotImplementedError("forward_batched covers the FPN configurations with the two-layer MLP head and the C4 ones")
         opt = getattr(self, "_opt_dtype", None)                 # optimize_for_inference(16-bit): weights live in that type
@@ -759,31 +786,22 @@ class detector(nn.Module):
             img_features = feats
         if proposals is not None:
             props = self._proposal_inputs(proposals, proposal_counts, B, dev)
-            path = self._region_path(B, h, w, dev, det_options, int(props[0].shape[1]))
-            self._box_stages(path, None, props, feats[:len(self.roi_spatial_scale)], img_features, sf, sz, blob_hw)
+            path = self._region_path(B, h, w, dev, det_options, int(props[0].shape[1]), view)
+            self._box_stages(path, None, props, feats[:len(self.roi_spatial_scale)], img_features, sf, sz, blob_hw, detect=view is None)
         else:
-            path = self._region_path(B, h, w, dev, det_options)
+            path = self._region_path(B, h, w, dev, det_options, view=view)
             rpn = ([c.float().contiguous() for c, _ in cls_bbox], [b.float().contiguous() for _, b in cls_bbox])
-            self._box_stages(path, rpn, None, feats, img_features, sf, sz, blob_hw)        # head: fc6 / fc7, [B*1000, 1024]
-        if self.use_mask_head:
-            mh = self.mask_head
-            probs = None
-            if opt is not None:
-                m = hip.bias_act_(_conv_nobias(mh.transposed_conv, mh.conv_head(path.mask_feats.to(opt))), _ebias(mh.transposed_conv))
-                # class logits: bias-free 1x1 conv, then bias + widening + NCHW layout in ONE pass, sigmoid in place
-                y = _conv_nobias(mh.classif_logits, m)
-                probs = torch.add(y, _ebias(mh.classif_logits).view(1, -1, 1, 1),
-                                  out=torch.empty(y.shape, dtype=torch.float32, device=dev)).sigmoid_()
-            elif self.head_dtype is not None and self.head_dtype != torch.float32:    # mask-head convs in the pooled features' type
-                with torch.autocast("cuda", dtype=self.head_dtype):
-                    m = mh.classif_logits(mh.relu(mh.transposed_conv(mh.conv_head(path.mask_feats.to(self.head_dtype)))))
-                m = m.float()
-            else:
-                m = mh.conv_head(path.mask_feats.float() if path.mask_feats.dtype != torch.float32 else path.mask_feats)
-                m = mh.classif_logits(mh.relu(mh.transposed_conv(m)))
-            path.bind_masks(probs if probs is not None else torch.sigmoid(m).contiguous())     # [B*128, 81, 28, 28]
+            self._box_stages(path, rpn, None, feats, img_features, sf, sz, blob_hw, detect=view is None)        # head: fc6 / fc7, [B*1000, 1024]
+        if self.use_mask_head and view is None:
+            path.bind_masks(self._mask_probs(path.mask_feats))                                 # [B*128, 81, 28, 28]
             path.launch_masks()
         return path
+
+    def forward_batched_aug(self, raw_images, aug=None, **kw):
+        """forward_batched with test-time augmentation (utils/test_aug.py:detect_aug): raw HWC BGR images in, the fixed-shape path
+        object of the identity view out, its detections and masks merged over mirrored and rescaled views."""
+        from ..utils.test_aug import detect_aug
+        return detect_aug(self, raw_images, aug, **kw)
 
     @staticmethod
     def per_image(path, b):

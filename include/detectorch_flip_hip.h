@@ -15,7 +15,8 @@
  *     widths of entries 2-4 are device data; dtc_flip_prep_images' flags are baked into the captured kernel arguments),
  *   - no input value is used as an address unchecked.
  * Exact arithmetic only (two float32 subtractions, two float64 subtractions and a cast, integers): the same bits on every run.
- * Out of scope: scale jitter, keypoint flipping (commented out in the reference), flip test-time augmentation.
+ * Out of scope: scale jitter, keypoint flipping (commented out in the reference).  (Flip test-time augmentation is
+ * detectorch_aug_hip.h's.)
  */
 #ifndef DETECTORCH_FLIP_HIP_H_
 #define DETECTORCH_FLIP_HIP_H_
