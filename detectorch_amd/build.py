@@ -14,7 +14,7 @@ operators (csrc/grad/*.hip -> libdetectorch_grad_hip.so), build_optim() for the 
 polygons and run lists (csrc/flip/*.hip -> libdetectorch_flip_hip.so), build_mpost() for mask post-processing on run lists: mask
 boxes, mask overlaps, mask NMS and mask voting (csrc/mask_post/*.hip -> libdetectorch_mpost_hip.so), build_aug() for test-time
 augmentation: the merge of the views' box-head outputs and the combination of their mask probabilities (csrc/aug/*.hip ->
-libdetectorch_aug_hip.so).
+libdetectorch_aug_hip.so), build_kps() for keypoint inference: heatmaps to keypoints (csrc/kps/*.hip -> libdetectorch_kps_hip.so).
 
 No torch headers, no hipify, no multi-arch: one code object for gfx950.  -ffp-contract=off is part of the numerics
 contract (see csrc/dtc_common.h).
@@ -88,7 +88,7 @@ def build(force=False, verbose=False):
 # (include/detectorch_rpn_hip.h), mask training (include/detectorch_mask_hip.h), scoring (include/detectorch_eval_hip.h), scoring
 # masks (include/detectorch_segm_hip.h), polygons to run lists (include/detectorch_poly_hip.h), the horizontal flip
 # (include/detectorch_flip_hip.h), mask post-processing (include/detectorch_mpost_hip.h) and test-time augmentation
-# (include/detectorch_aug_hip.h).  sources()
+# (include/detectorch_aug_hip.h), keypoint inference (include/detectorch_kps_hip.h; csrc/kps/*.hip).  sources()
 # globs csrc/*.hip only; csrc/train/*.hip, csrc/loss/*.hip, csrc/grad/*.hip, csrc/optim/*.hip, csrc/rpn_train/*.hip, csrc/mask_train/*.hip,
 # csrc/eval/*.hip, csrc/segm_eval/*.hip, csrc/poly_rle/*.hip, csrc/flip/*.hip, csrc/mask_post/*.hip and csrc/aug/*.hip include the csrc/ headers by include path and are built with the same
 # FLAGS, one library per directory.
@@ -116,6 +116,8 @@ MPOST_CSRC = os.path.join(CSRC, "mask_post")                 # mask post-process
 MPOST_LIB = os.path.join(LIBDIR, "libdetectorch_mpost_hip.so")
 AUG_CSRC = os.path.join(CSRC, "aug")                         # test-time augmentation (include/detectorch_aug_hip.h): merge of the views' boxes, combination of their masks
 AUG_LIB = os.path.join(LIBDIR, "libdetectorch_aug_hip.so")
+KPS_CSRC = os.path.join(CSRC, "kps")                         # keypoint inference (include/detectorch_kps_hip.h): heatmaps to keypoints
+KPS_LIB = os.path.join(LIBDIR, "libdetectorch_kps_hip.so")
 
 
 def _side_sources(csrc):
@@ -205,6 +207,10 @@ def build_aug(force=False, verbose=False):
     return _build_side(AUG_LIB, AUG_CSRC, force, verbose)
 
 
+def build_kps(force=False, verbose=False):
+    return _build_side(KPS_LIB, KPS_CSRC, force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_train(force="--force" in sys.argv, verbose=True))
@@ -219,3 +225,4 @@ if __name__ == "__main__":
     print(build_flip(force="--force" in sys.argv, verbose=True))
     print(build_mpost(force="--force" in sys.argv, verbose=True))
     print(build_aug(force="--force" in sys.argv, verbose=True))
+    print(build_kps(force="--force" in sys.argv, verbose=True))

@@ -249,6 +249,30 @@ class mask_head(nn.Module):
         return torch.sigmoid(x) if self.output_prob else x
 
 
+class keypoint_head(nn.Module):
+    """Detectron's keypoint_rcnn_heads.py:add_roi_pose_head_v1convX with its outputs (add_keypoint_outputs, USE_DECONV_OUTPUT and
+    UP_SCALE = 2): eight 3x3 convs of 512 channels with ReLU on the 14x14 pooled features, ConvTranspose2d(512, K, 4, 2, 1) to 28x28 and
+    the fixed-weight bilinear x2 deconvolution (a per-channel ConvTranspose2d(4, 2, 1) with upsample_filt(4) = outer([.25, .75, .75,
+    .25]) and no bias) to K maps of 56x56 LOGITS.  Float32; the weights have no caffe2 names here."""
+
+    def __init__(self, num_keypoints=17, in_channels=256, channels=512):
+        super().__init__()
+        self.num_keypoints = int(num_keypoints)
+        self.relu = nn.ReLU(inplace=True)
+        for i in range(8):
+            setattr(self, 'conv_fcn%d' % (i + 1), nn.Conv2d(in_channels if i == 0 else channels, channels, 3, padding=1))
+        self.kps_score_lowres = nn.ConvTranspose2d(channels, self.num_keypoints, 4, stride=2, padding=1)
+        f = torch.tensor([0.25, 0.75, 0.75, 0.25])
+        # not a parameter and not in state_dict: BilinearInterpolation's weights are fixed
+        self.register_buffer('up_filter', (f[:, None] * f[None, :]).expand(self.num_keypoints, 1, 4, 4).contiguous(), persistent=False)
+
+    def forward(self, x):
+        for i in range(8):
+            x = self.relu(getattr(self, 'conv_fcn%d' % (i + 1))(x))
+        x = self.kps_score_lowres(x)
+        return F.conv_transpose2d(x, self.up_filter, stride=2, padding=1, groups=self.num_keypoints)
+
+
 class rpn_head(nn.Module):
     def __init__(self, in_channels=1024, out_channels=1024, n_anchors=15):
         super().__init__()
@@ -300,7 +324,7 @@ class detector(nn.Module):
                  use_mask_head=False, mask_head_type='upshare', roi_feature_channels=2048, N_classes=81,
                  detector_pkl_file=None, base_cnn_pkl_file=None, output_prob=True, roi_height=14, roi_width=14,
                  roi_spatial_scale=0.0625, roi_sampling_ratio=0, channels_last=False, fuse_rpn_sigmoid=True,
-                 head_dtype=None, backbone_dtype=None):
+                 head_dtype=None, backbone_dtype=None, use_keypoint_head=False, num_keypoints=17, person_class=1):
         super().__init__()
         self.fuse_rpn_sigmoid = bool(fuse_rpn_sigmoid)   # extension: RPN sigmoid folded into the top-k kernel (same outputs)
         self.head_dtype = head_dtype    # extension: torch.bfloat16 / float16 -> pooled features + fc6/fc7 in that dtype (MFMA GEMMs)
@@ -357,6 +381,10 @@ class detector(nn.Module):
         if self.use_mask_head:
             mh_conv = self.conv_head[0] if mask_head_type == 'upshare' else four_layer_conv()
             self.mask_head = mask_head(mh_conv, self.roi_spatial_scale, self.roi_sampling_ratio, output_prob)
+        # extension (forward_batched, FPN): Detectron's keypoint branch on the detections of person_class (tests/README_keypoints.md)
+        self.use_keypoint_head, self.person_class = bool(use_keypoint_head), int(person_class)
+        if self.use_keypoint_head:
+            self.keypoint_head = keypoint_head(num_keypoints)
         if detector_pkl_file is not None:
             self.load_pretrained_weights(detector_pkl_file, model='detector')
         elif base_cnn_pkl_file is not None:
@@ -748,13 +776,18 @@ class detector(nn.Module):
         preprocess_sample.py:35-45); N <= 2048.
         view (utils/test_aug.py): not None makes this call one VIEW of a test-time-augmented batch -- it gets a region path of its
         own under that key and stops after the box-head outputs (path.cls_logits_out / bbox_pred_out on path.rois5): no detection
-        stage, no mask branch."""
+        stage, no mask branch.
+        use_keypoint_head=True (FPN, float32, NCHW, not optimised; NotImplementedError otherwise): after the detections the keypoint
+        head runs on the same 14x14 pooled features and leaves path.kp_heatmaps [B*max_out, K, 56, 56], path.keyps [B, max_out, 4, K]
+        = x, y, logit, prob and path.kp_status [B, max_out] (_keypoints)."""
         if self.use_rpn_head and proposals is not None:
             raise ValueError("this model has an RPN head: its proposals come from it (proposals= is for models without one)")
         if not self.use_rpn_head and proposals is None:
             raise ValueError("a model without an RPN head needs precomputed proposals (proposals=)")
         if bbox_vote_method not in hip.VOTE_METHODS:
             raise NotImplementedError('Unknown scoring method {}'.format(bbox_vote_method))      # boxes.py:324-327
+        if self.use_keypoint_head:
+            self._check_keypoint_config()
         det_options = None
         if do_soft_nms or do_bbox_vote:
             det_options = dict(do_soft_nms=bool(do_soft_nms), soft_nms_sigma=float(soft_nms_sigma), soft_nms_method=soft_nms_method,
@@ -795,7 +828,30 @@ class detector(nn.Module):
         if self.use_mask_head and view is None:
             path.bind_masks(self._mask_probs(path.mask_feats))                                 # [B*128, 81, 28, 28]
             path.launch_masks()
+        if self.use_keypoint_head and view is None:
+            self._keypoints(path)
         return path
+
+    def _check_keypoint_config(self):
+        if (not self.use_fpn_body or self.channels_last or getattr(self, "_optimized", False)
+                or self.head_dtype not in (None, torch.float32) or self.backbone_dtype not in (None, torch.float32)):
+            raise NotImplementedError("the keypoint head covers the FPN models in float32, NCHW, not optimised")
+
+    def _keypoints(self, path):
+        """The keypoint branch of the FPN models in float32, NCHW, not optimised: keypoint_head on the 14x14 pooled features of the
+        detections (path.mask_feats, which the FPN path pools with or without a mask head) -> path.kp_heatmaps [B*max_out, K, 56, 56]
+        logits -> dtc_kps_heatmaps_to_keypoints on path.dets / path.det_count -> path.keyps [B, max_out, 4, K] and path.kp_status
+        [B, max_out] (1 for the rows of person_class below the count).  No host sync.  Anything else raises NotImplementedError."""
+        self._check_keypoint_config()
+        from .. import hip_kps
+        path.kp_heatmaps = self.keypoint_head(path.mask_feats).contiguous()
+        K = path.kp_heatmaps.shape[1]
+        if getattr(path, "kp_out", None) is None or path.kp_out["keyps"].shape[3] != K:
+            path.kp_out = hip_kps.keypoint_outputs(path.B, path.max_out, K, path.dev)
+            path.kp_ws = hip_kps.workspace(path.B, path.max_out, K, path.dev)
+        hip_kps.heatmaps_to_keypoints(path.kp_heatmaps, path.dets, path.det_count, person_class=self.person_class, out=path.kp_out,
+                                      ws=path.kp_ws)
+        path.keyps, path.kp_status = path.kp_out["keyps"], path.kp_out["kp_status"]
 
     def forward_batched_aug(self, raw_images, aug=None, **kw):
         """forward_batched with test-time augmentation (utils/test_aug.py:detect_aug): raw HWC BGR images in, the fixed-shape path

@@ -8,6 +8,7 @@ the arithmetic done by the HIP kernels (detectorch_amd/csrc/detections.hip, nms.
     assemble_results                the eval loop's per-image empty_results / extend_results bookkeeping (eval_mask_FPN.ipynb
                                     cell 6) for a whole (gathered) batch of fixed-shape device results
     coco_bbox_results / coco_segm_results   the records of lib/utils/json_dataset_evaluator.py:67-113, 149-190
+    coco_keypoint_results           the records of lib/utils/json_dataset_evaluator.py:349-416
 """
 import numpy as np
 import torch
@@ -235,7 +236,7 @@ def segm_results(cls_boxes, masks, ref_boxes, im_h, im_w, num_classes=81, M=14, 
 
 
 def assemble_results(dets, det_count, im_sizes=None, rle_str=None, rle_len=None, num_classes=81, all_boxes=None,
-                     all_segms=None, first_image=0, on_overflow="raise"):
+                     all_segms=None, first_image=0, on_overflow="raise", keyps=None, kp_status=None, all_keyps=None, person_class=1):
     """all_boxes / all_segms (result_utils.py:32-60) from the fixed-shape outputs of the batched path.
 
       dets [N, max_out, 6] = (x1,y1,x2,y2,score,class) class-major per image, det_count [N]   (dtc_postprocess_detections,
@@ -246,13 +247,24 @@ def assemble_results(dets, det_count, im_sizes=None, rle_str=None, rle_len=None,
     correspondence -- exactly what `extend_results(i, all_boxes, cls_boxes_i)` / `extend_results(i, all_segms, cls_segms_i)`
     leave behind image by image in the reference's eval loop.  Pass all_boxes / all_segms / first_image to fill a slice of
     existing lists (e.g. the shard of one rank).  on_overflow: an image with more detections (ties at the image threshold) than the
-    max_out fixed rows raises ("raise", default) or keeps the first max_out rows with a RuntimeWarning ("truncate")."""
+    max_out fixed rows raises ("raise", default) or keeps the first max_out rows with a RuntimeWarning ("truncate").
+
+      keyps [N, max_out, 4, K] + kp_status [N, max_out] (dtc_kps_heatmaps_to_keypoints): optional.  With them
+      all_keyps[person_class][image] = list of [4, K] arrays (x, y, logit, prob) in the order of all_boxes[person_class][image] (what
+      extend_results(i, all_keyps, cls_keyps_i) leaves behind), and (all_boxes, all_segms, all_keyps) is returned; pass all_keyps to
+      fill a slice of an existing list.  A person row that was not computed (status 0: another person_class was given to the
+      kernel; -1: refused) raises."""
     if on_overflow not in ("raise", "truncate"):
         raise ValueError("on_overflow must be 'raise' or 'truncate'")
     dets, det_count = to_np(dets), to_np(det_count).reshape(-1)
     N, max_out = dets.shape[0], dets.shape[1]
     if all_boxes is None:
         all_boxes, all_segms, _ = empty_results(num_classes, first_image + N)
+    want_keyps = keyps is not None
+    if want_keyps:
+        keyps, kp_status = to_np(keyps), to_np(kp_status).reshape(N, -1)
+        if all_keyps is None:
+            all_keyps = empty_results(num_classes, first_image + N)[2]
     want_segms = rle_str is not None
     if want_segms:
         rle_str, rle_len = to_np(rle_str), to_np(rle_len).reshape(N, -1)
@@ -282,6 +294,13 @@ def assemble_results(dets, det_count, im_sizes=None, rle_str=None, rle_len=None,
                                            % (first_image + i, k, rle_len[i, k], rle_str.shape[2]))
                     segs.append({'size': [h, w], 'counts': rle_str[i, k, :rle_len[i, k]].tobytes().decode('ascii')})
                 all_segms[j][first_image + i] = segs
+            if want_keyps and j == person_class:
+                if (kp_status[i, sel] != 1).any():
+                    raise RuntimeError("image %d: keypoints of detections %s were not computed (kp_status %s)" % (
+                        first_image + i, sel[kp_status[i, sel] != 1].tolist(), kp_status[i, sel][kp_status[i, sel] != 1].tolist()))
+                all_keyps[j][first_image + i] = [np.ascontiguousarray(keyps[i, k]) for k in sel]
+    if want_keyps:
+        return all_boxes, all_segms, all_keyps
     return all_boxes, all_segms
 
 
@@ -313,4 +332,32 @@ def coco_segm_results(all_boxes, all_segms, image_ids, class_to_cat_id):
             assert len(rles) == d.shape[0]
             res.extend({'image_id': image_id, 'category_id': class_to_cat_id[j], 'segmentation': rles[k], 'score': d[k, -1]}
                        for k in range(d.shape[0]))
+    return res
+
+
+def coco_keypoint_results(all_boxes, all_keyps, image_ids, cat_id, confidence='bbox'):
+    """The records _write_coco_keypoint_results_file dumps for one category (json_dataset_evaluator.py:371-416): all_boxes / all_keyps
+    are the per-image lists of that class (all_boxes[person], all_keyps[person]).  Every keypoint is written as (x, y, 1); the score is
+    the mean keypoint logit ('logit'), the mean keypoint probability ('prob') or the box score ('bbox'), KRCNN.KEYPOINT_CONFIDENCE."""
+    if confidence not in ('logit', 'prob', 'bbox'):
+        raise ValueError('KRCNN.KEYPOINT_CONFIDENCE must be "logit", "prob", or "bbox"')
+    assert len(all_keyps) == len(image_ids) and len(all_boxes) == len(image_ids)
+    score_index = {'logit': 2, 'prob': 3}.get(confidence)
+    res = []
+    for i, image_id in enumerate(image_ids):
+        if len(all_boxes[i]) == 0 or len(all_keyps[i]) == 0:
+            continue
+        scores = np.asarray(all_boxes[i])[:, -1].astype(np.float64)
+        for j, kps in enumerate(all_keyps[i]):
+            xy = []
+            for k in range(kps.shape[1]):
+                xy.extend([float(kps[0, k]), float(kps[1, k]), 1])
+            if score_index is None:
+                score = scores[j]
+            else:
+                score = 0
+                for k in range(kps.shape[1]):
+                    score += kps[score_index, k]
+                score /= kps.shape[1]
+            res.append({'image_id': image_id, 'category_id': cat_id, 'keypoints': xy, 'score': score})
     return res
